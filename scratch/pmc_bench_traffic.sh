@@ -2,8 +2,9 @@
 # HBM traffic of the dominant kernel family over bench.py's workload: FETCH_SIZE and WRITE_SIZE in SEPARATE --pmc
 # passes (MI355X_MICROARCH.md: TCC has 4 slots, the two need 3 + 2), units KB, FETCH_SIZE doubled on gfx950.
 export GANK_BENCH_EXTRAS=0     # bench.py: the headline measurement only
+# usage: scratch/pmc_bench_traffic.sh <output json, an absolute path>
+out=${1:?usage: pmc_bench_traffic.sh <output json>}
 cd /tmp && export TMPDIR=/tmp
-out=$GRAFT_REPO_ROOT/gpurun_out/traffic.json
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_b_$c
   timeout -k 10 280 rocprofv3 --pmc $c --output-format csv -d /tmp/pmc_b_$c -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --steps 3 --warmup 2 > /dev/null 2>&1 < /dev/null || { echo "pass $c failed"; exit 1; }
