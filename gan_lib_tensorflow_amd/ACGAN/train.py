@@ -210,3 +210,18 @@ class ACGANTrainer:
         self.global_step_counter = step + 1
 
     global_step_counter = 0
+
+    @torch.no_grad()
+    def msssim_diversity(self, n_pairs=500, weights=None):
+        """Per-class sample diversity, the measure of the ACGAN paper: MS-SSIM (common/msssim.py of the reference) between pairs
+        of same-class samples.  Batches of `batch_size` samples on fresh noise and uniform labels (the draws of g_loss), quantised
+        as `((x + 1) * (255.99 / 2))` truncated to uint8, until every class has 2 * n_pairs samples; consecutive same-class
+        samples are paired.  -> ({class: batch MultiScaleSSIM of its n_pairs pairs}, mean over classes).  Low = diverse."""
+        from ..common.msssim import class_pair_diversity, quantize_on_device
+        set_default_store(self.store)
+
+        def draw():
+            z = K.rng_normal((self.batch, self.z_dim), self.rng_state)
+            labels = K.rng_labels(self.batch, 10, self.rng_state)
+            return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3), labels
+        return class_pair_diversity(draw, n_pairs, 10, weights)

@@ -173,3 +173,12 @@ class Pix2PixTrainer:
         for _ in range(self.args.n_dis):
             self.d_step(inputs, targets)
         return self.g_step(inputs, targets)
+
+
+@torch.no_grad()
+def msssim_score(outputs, targets, weights=None, per_image=False):
+    """MS-SSIM (common/msssim.py of the reference) of generator outputs against their targets, both [N,H,W,C] in [-1, 1] as the
+    model produces / is fed them (any 16-bit or fp32 dtype, any size up to the 512 x 512 crops): scored as fp32 with max_val = 2
+    after the shift to [0, 2].  One float with the reference's batch semantics, or float64 [N] with per_image=True."""
+    from ..common.msssim import MultiScaleSSIM
+    return MultiScaleSSIM(outputs.float() + 1.0, targets.float() + 1.0, max_val=2.0, weights=weights, per_image=per_image)

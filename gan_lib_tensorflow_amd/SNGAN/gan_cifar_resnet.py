@@ -972,6 +972,20 @@ class SNGANTrainer:
             labels = K.rng_labels(n, 10, self.rng_state)
         return Generator(n, labels, noise=noise, groups=1, rng_state=self.rng_state)
 
+    @torch.no_grad()
+    def msssim_diversity(self, n_pairs=500, weights=None):
+        """Per-class sample diversity (the ACGAN paper's mode-collapse measure; MS-SSIM is an evaluation TODO of the reference's
+        README, common/msssim.py): samples come through the IS sampling path -- `sample(100)` on fresh uniform labels, so the
+        conditional batch norm sees the mixed-label batch statistics it sees everywhere else --, quantised on the device as for
+        the score (:551), until every class has 2 * n_pairs of them; consecutive same-class samples are paired.
+        -> ({class: batch MultiScaleSSIM of its n_pairs pairs}, mean over classes).  Low = diverse."""
+        from ..common.msssim import class_pair_diversity, quantize_on_device
+
+        def draw():
+            labels = K.rng_labels(100, 10, self.rng_state)
+            return quantize_on_device(self.sample(100, labels)).reshape(-1, 32, 32, 3), labels
+        return class_pair_diversity(draw, n_pairs, 10, weights)
+
 
 def _inception_score_of(trainer, n, classifier, splits, batch_size):
     """(:543-555)  n / 100 calls of `samples_100` -- a Generator(100, ...) pass on fresh uniform labels and fresh noise, batch

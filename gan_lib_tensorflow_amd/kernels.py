@@ -1859,6 +1859,35 @@ def tr_probe(device):
     return out
 
 
+# ------------------------------------------------------------------ MS-SSIM (common/msssim.py)
+def msssim_level_parts(h, w, c, size):
+    n = lib().gank_msssim_level_parts(h, w, c, size)
+    if n <= 0:
+        _lib.check(1, "msssim_level_parts")
+    return n
+
+
+def msssim_level(img1, img2, taps, c1, c2, offset, part, pool=True):
+    """One pyramid level of MS-SSIM for a batch of pairs (gank_msssim_level).  img1, img2: uint8 or fp32 [N,H,W,C]; taps: the
+    1-D window (host floats, len <= 11); part: fp32 [N, msssim_level_parts(H, W, C, len(taps)), 2], receives per image and tile
+    the sums of the ssim and cs maps.  -> the 2x2-pooled fp32 pair [N,ceil(H/2),ceil(W/2),C] of the next level, or (None, None)"""
+    n, h, w, c = img1.shape
+    dt = img1.dtype
+    if dt not in (torch.uint8, F32):
+        raise RuntimeError(f"gank: msssim_level takes uint8 or float32 images, got {dt}")
+    size = len(taps)
+    if img2.shape != img1.shape or part.numel() != n * msssim_level_parts(h, w, c, size) * 2:
+        raise RuntimeError(f"gank: msssim_level: img2 {tuple(img2.shape)} / part {tuple(part.shape)} do not fit img1 {tuple(img1.shape)}")
+    p1 = p2 = None
+    if pool:
+        p1 = torch.empty((n, (h + 1) // 2, (w + 1) // 2, c), dtype=F32, device=img1.device)
+        p2 = torch.empty_like(p1)
+    ktaps = (C.c_float * size)(*[float(t) for t in taps])
+    _lib.check(lib().gank_msssim_level(_p(img1, dt, "img1"), _p(img2, dt, "img2"), 0 if dt == torch.uint8 else 1, n, h, w, c, size, ktaps,
+                                       c1, c2, offset, _p(part, F32, "part"), _p(p1), _p(p2), _stream()), "msssim_level")
+    return p1, p2
+
+
 # ------------------------------------------------------------------ profiler
 def prof_enable(on):
     lib().gank_prof_enable(int(on))

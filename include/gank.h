@@ -859,6 +859,23 @@ int gank_fewout_pack(const float* src, float* dst, int ksize, int Cin, int Cout,
 /* fp32 zero fill (scratch gradients of the routes above) */
 int gank_zero_f32(float* p, long n, void* stream);
 
+/* ---- MS-SSIM, one pyramid level per launch (common/msssim.py:50-123,181-183) ---------------------------------------
+ * gank_msssim_level: for N image pairs img1 / img2 [N,H,W,C] (dtype 0 = uint8, 1 = float32; NHWC) the Gaussian-windowed
+ *   SSIM of _SSIMForMultiScale (:50-123) with a size x size window = outer product of the `size` 1-D `taps`
+ *   (taps: HOST pointer, copied into the kernel arguments; 1 <= size <= 11 <= H, W), VALID blur, c1 = (k1*max_val)^2,
+ *   c2 = (k2*max_val)^2.  `offset` (max_val / 2) is subtracted from every pixel before the moments are formed and added back
+ *   to the means only (the variances are shift invariant; fp32 cancels far less this way).
+ *   part: fp32 [N][P][2], P = gank_msssim_level_parts(H, W, C, size): per image and tile the SUMS of the ssim map (index 0)
+ *   and of the cs map (index 1) over the tile's part of the (H-size+1) x (W-size+1) x C output positions; every entry is
+ *   written (no pre-zeroing, no atomics: bit-reproducible); the caller adds the P partials of an image in a fixed order.
+ *   pool1 / pool2: fp32 [N,ceil(H/2),ceil(W/2),C] or both NULL: the input of the next level (:181-183: the 2x2 box filter
+ *   of scipy.ndimage.convolve(mode='reflect') sampled at even positions = the mean of x[2i..2i+1][2j..2j+1], the last row /
+ *   column replicated when H / W is odd), written by the same launch.
+ * gank_msssim_level_parts: P for a shape; 0 (with a message) for a shape gank_msssim_level refuses. */
+int gank_msssim_level(const void* img1, const void* img2, int dtype, int N, int H, int W, int C, int size, const float* taps,
+                      float c1, float c2, float offset, float* part, float* pool1, float* pool2, void* stream);
+int gank_msssim_level_parts(int H, int W, int C, int size);
+
 #ifdef __cplusplus
 }
 #endif
