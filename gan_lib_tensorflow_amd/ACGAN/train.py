@@ -20,7 +20,7 @@ from .. import functional2 as F2
 from .. import kernels as K
 from .. import parallel
 from ..graphs import GraphRunner
-from ..store import ParamStore, set_default_store
+from ..store import ParamStore, adam_state, set_default_store
 from .model import ACGAN
 
 
@@ -78,8 +78,8 @@ class ACGANTrainer:
         for p in self.d_params:
             p.grad = p.main_grad         # the twice-differentiable critic RETURNS weight gradients: autograd adds them in place here
             del p.main_grad
-        self.g_opt = self._adam(self.g_flat)
-        self.d_opt = self._adam(self.d_flat)
+        self.g_opt = adam_state(self.g_flat, 0.0004, 0.0, 0.9, self.world)
+        self.d_opt = adam_state(self.d_flat, 0.0004, 0.0, 0.9, self.world)
         self._g_convs = [(k, v) for k, v in self.store.vars.items() if k.startswith('g_net/') and k.endswith('/Filters') and v.dim() == 4]
         self._refresh_g_prep()
         self.losses = {}
@@ -88,14 +88,6 @@ class ACGANTrainer:
         self.graphs = GraphRunner(use_graphs, allow_eager_fallback)     # a failed hipGraph capture raises unless the caller allows eager execution
         self.real_u8 = torch.zeros((batch_size, 3072), dtype=torch.uint8, device=self.device)
         self.real_labels = torch.zeros(batch_size, dtype=torch.int32, device=self.device)
-
-    def _adam(self, flat):
-        dev = self.device
-        return dict(hp=torch.tensor([0.0004, 0.0, 0.9, 1e-8, 1.0 / self.world, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev),
-                    t=torch.zeros(1, dtype=torch.int64, device=dev), flat=flat)
-
-    def _set_lr(self, opt):
-        opt['hp'][0:1].fill_(polynomial_decay(self.global_step, decay_steps=self.max_iter // 2))
 
     def _apply(self, opt):
         f = opt['flat']
@@ -111,14 +103,9 @@ class ACGANTrainer:
             K.prep_weights_batched([v for _, v in self._g_convs], want_d=True, kinds=[_g_prep_kind(k, v) for k, v in self._g_convs])
 
     def _update(self, key, fwd_bwd, opt):
-        """fwd_bwd (graph) -> [RCCL all-reduce] -> Adam (graph): one graph when there is nothing to exchange"""
-        self._set_lr(opt)
-        if self.world == 1:
-            self.graphs.run(key, lambda: (fwd_bwd(), self._apply(opt)))
-        else:
-            self.graphs.run(key, fwd_bwd)
-            parallel.allreduce_sum_(opt['flat']['grads'], self.pg)
-            self.graphs.run(key + '/adam', lambda: self._apply(opt))
+        """the decayed learning rate, written outside the captured region, then GraphRunner.update"""
+        opt['hp'][0:1].fill_(polynomial_decay(self.global_step, decay_steps=self.max_iter // 2))
+        self.graphs.update(key, fwd_bwd, lambda: self._apply(opt), opt['flat']['grads'], self.pg, self.world)
 
     # ---- the two losses (eager; explicit inputs override the device RNG for parity tests) -----------------------------
     def d_loss(self, real, real_labels, z=None, fake_labels=None, alpha=None):

@@ -17,7 +17,7 @@ from .. import functional as Fn
 from .. import kernels as K
 from .. import parallel
 from ..graphs import GraphRunner
-from ..store import ParamStore, set_default_store
+from ..store import ParamStore, adam_state, set_default_store
 from .model_nvidia import PGGAN
 
 
@@ -53,31 +53,21 @@ class PGGANTrainer:
         self.d_flat = self.store.flatten('d_net')
         self.g_params = [self.store.vars[k] for k in self.g_flat['names']]
         self.d_params = [self.store.vars[k] for k in self.d_flat['names']]
-        self.g_opt = self._adam(self.g_flat)
-        self.d_opt = self._adam(self.d_flat)
+        self.g_opt = adam_state(self.g_flat, 0.0001, 0.0, 0.9, self.world)
+        self.d_opt = adam_state(self.d_flat, 0.0001, 0.0, 0.9, self.world)
         self.losses = {}
         # the two updates as captured hipGraphs: static input rows, the fade-in weight in device memory (written before a replay)
         self.graphs = GraphRunner(use_graphs, allow_eager_fallback)     # a failed hipGraph capture raises unless the caller allows eager execution
         self.real_u8 = torch.zeros((args.batch_size, args.image_dim), dtype=torch.uint8, device=self.device)
         self.alpha_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
 
-    def _adam(self, flat):
-        dev = self.device
-        return dict(hp=torch.tensor([0.0001, 0.0, 0.9, 1e-8, 1.0 / self.world, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev),
-                    t=torch.zeros(1, dtype=torch.int64, device=dev), flat=flat)
-
     def _apply(self, opt):
         f = opt['flat']
         K.adam_tf(f['params'], f['grads'], f['m'], f['v'], opt['hp'], opt['t'], None, zero_grads=True)
 
     def _update(self, key, fwd_bwd, opt):
-        """fwd_bwd (graph) -> [RCCL all-reduce] -> Adam (graph): one graph when there is nothing to exchange"""
-        if self.world == 1:
-            self.graphs.run(key, lambda: (fwd_bwd(), self._apply(opt)))
-        else:
-            self.graphs.run(key, fwd_bwd)
-            parallel.allreduce_sum_(opt['flat']['grads'], self.pg)
-            self.graphs.run(key + '/adam', lambda: self._apply(opt))
+        """GraphRunner.update: fwd_bwd (graph) -> [RCCL all-reduce] -> Adam (graph)"""
+        self.graphs.update(key, fwd_bwd, lambda: self._apply(opt), opt['flat']['grads'], self.pg, self.world)
 
     def alpha(self, step=None):
         return float(self.step if step is None else step) / float(self.args.max_iter)        # feed_dict alpha (:186)

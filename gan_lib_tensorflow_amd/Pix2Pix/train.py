@@ -17,7 +17,7 @@ from .. import functional as Fn
 from .. import kernels as K
 from .. import parallel
 from ..graphs import GraphRunner
-from ..store import ParamStore, set_default_store
+from ..store import ParamStore, adam_state, set_default_store
 from .model import Pix2Pix
 
 
@@ -62,8 +62,8 @@ class Pix2PixTrainer:
         self.d_flat = self.store.flatten('d_net')
         self.g_params = [self.store.vars[k] for k in self.g_flat['names']]
         self.d_params = [self.store.vars[k] for k in self.d_flat['names']]
-        self.g_opt = self._adam(self.g_flat)
-        self.d_opt = self._adam(self.d_flat)
+        self.g_opt = adam_state(self.g_flat, args.initial_lr, args.beta1, args.beta2, self.world)
+        self.d_opt = adam_state(self.d_flat, args.initial_lr, args.beta1, args.beta2, self.world)
         self.losses = {}
         # the two updates as captured hipGraphs: static input / target buffers, the learning rate written outside the capture
         self.graphs = GraphRunner(use_graphs, allow_eager_fallback)     # a failed hipGraph capture raises unless the caller allows eager execution
@@ -81,26 +81,15 @@ class Pix2PixTrainer:
                                             conv_type=a.conv_type, channel_multiplier=a.channel_multiplier, padding='VALID',
                                             net_type=a.net_type, reuse=reuse)
 
-    def _adam(self, flat):
-        dev = self.device
-        return dict(hp=torch.tensor([self.args.initial_lr, self.args.beta1, self.args.beta2, 1e-8, 1.0 / self.world, 0.0, 0.0, 0.0],
-                                    dtype=torch.float32, device=dev),
-                    t=torch.zeros(1, dtype=torch.int64, device=dev), flat=flat)
-
     def _apply(self, opt):
         f = opt['flat']
         K.adam_tf(f['params'], f['grads'], f['m'], f['v'], opt['hp'], opt['t'], None, zero_grads=True)
 
     def _update(self, key, fwd_bwd, opt):
-        """fwd_bwd (graph) -> [RCCL all-reduce] -> Adam (graph): one graph when there is nothing to exchange"""
+        """the decayed learning rate, written outside the captured region, then GraphRunner.update"""
         a = self.args
         opt['hp'][0:1].fill_(polynomial_decay(self.global_step, a.initial_lr, a.max_steps, a.end_lr))
-        if self.world == 1:
-            self.graphs.run(key, lambda: (fwd_bwd(), self._apply(opt)))
-        else:
-            self.graphs.run(key, fwd_bwd)
-            parallel.allreduce_sum_(opt['flat']['grads'], self.pg)
-            self.graphs.run(key + '/adam', lambda: self._apply(opt))
+        self.graphs.update(key, fwd_bwd, lambda: self._apply(opt), opt['flat']['grads'], self.pg, self.world)
 
     # ---- losses ---------------------------------------------------------------------------------------------------
     def d_loss(self, inputs, targets):

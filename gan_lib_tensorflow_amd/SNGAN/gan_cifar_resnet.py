@@ -17,14 +17,15 @@ MI355X-first structure
     draw fresh noise / labels / dequantisation.
 """
 import contextlib
-import gc
 import math
+import sys
 
 import numpy as np
 import torch
 import torch.distributed as _dist
 
 from .. import functional as Fn
+from .. import graphs
 from .. import kernels as K
 from .. import parallel
 from ..common import resnet_block as blocks
@@ -289,22 +290,6 @@ class AdamTF:
                 self.sn_state.valid = False
             K.adam_tf(f["params"], f["grads_all"], f["m"], f["v"], self.hp, self.t, self.iteration, zero_grads=True, health=self.health)
         f["clean"] = True
-
-
-@contextlib.contextmanager
-def _capture(graph):
-    """hipGraph capture with the Python garbage collector paused: a cyclic-GC pass in the middle of a capture can
-    destroy an older trainer's CUDAGraph / return its pool memory while the stream is capturing, which aborts the
-    process (torch only collects once, on entry)."""
-    was = gc.isenabled()
-    parallel.drain_collective_watchdog()
-    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-        gc.disable()
-        try:
-            yield
-        finally:
-            if was:
-                gc.enable()
 
 
 class SNGANTrainer:
@@ -688,78 +673,42 @@ class SNGANTrainer:
             if i == last - 1:
                 gb.join()              # the optimiser phase reads every bucket
 
-        if not self.use_graphs:
+        if self.use_graphs and 'g_seg' in self._graphs:
+            self._ensure_clean(self.g_flat)
+            self._ensure_sn_state()
+            if isinstance(self._graphs['g_seg'], torch.cuda.CUDAGraph):
+                self._graphs['g_seg'].replay()
+            else:
+                for i, g in enumerate(self._graphs['g_seg']):
+                    g.replay()
+                    between(i)
+            self.g_flat["clean"] = True
+            return
+
+        def update():                           # every phase AND the bucket all-reduces (forked onto the communication stream)
             for i, ph in enumerate(phases):
                 ph()
                 between(i)
+        if not self.use_graphs:
+            update()
             return
-        if 'g_seg' not in self._graphs:
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):          # eager first execution (this IS the update), exactly as _run does
-                for i, ph in enumerate(phases):
+        graphs.eager_on_side_stream(update)     # eager first execution (this IS the update), exactly as _run does
+        if self.capture_collectives:
+            g = self._capture_whole('bucketed generator update', update)
+            if g is not None:
+                self._graphs['g_seg'] = g
+                return
+        try:
+            pool = torch.cuda.graph_pool_handle()
+            seg = []
+            for ph in phases:                   # one graph per phase, one memory pool: later phases read what earlier ones made
+                with graphs.capture(pool) as g:
                     ph()
-                    between(i)
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            if self.capture_collectives:
-                try:
-                    g = torch.cuda.CUDAGraph()
-                    with _capture(g):           # every phase AND the bucket all-reduces (forked onto the communication stream): ONE graph
-                        for i, ph in enumerate(phases):
-                            ph()
-                            between(i)
-                    self._graphs['g_seg'] = g
-                except Exception as e:  # noqa: BLE001
-                    import sys
-                    torch.cuda.synchronize()
-                    print(f"[gank] capturing the bucketed generator update with its collectives failed ({e}); one graph per phase, "
-                          f"collectives between them", file=sys.stderr)
-                    self.capture_collectives = False
-                self._agree_on_capture()        # (entered with the same setting on every rank, so every rank calls this)
-                if isinstance(self._graphs.get('g_seg'), torch.cuda.CUDAGraph):
-                    if self.capture_collectives:
-                        return
-                    del self._graphs['g_seg']   # another rank could not capture its collectives: every rank takes the split form
-            try:
-                pool = torch.cuda.graph_pool_handle()
-                graphs = []
-                for ph in phases:               # one graph per phase, one memory pool: later phases read what earlier ones made
-                    g = torch.cuda.CUDAGraph()
-                    was = gc.isenabled()
-                    parallel.drain_collective_watchdog()
-                    with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
-                        gc.disable()
-                        try:
-                            ph()
-                        finally:
-                            if was:
-                                gc.enable()
-                    graphs.append(g)
-                self._graphs['g_seg'] = graphs
-            except Exception as e:  # noqa: BLE001
-                self._capture_failed('bucketed generator update', e)
-            return
-        self._ensure_clean(self.g_flat)
-        self._ensure_sn_state()
-        if isinstance(self._graphs['g_seg'], torch.cuda.CUDAGraph):
-            self._graphs['g_seg'].replay()
-        else:
-            for i, g in enumerate(self._graphs['g_seg']):
-                g.replay()
-                between(i)
-        self.g_flat["clean"] = True
-
-    def _capture_failed(self, what, e):
-        """The eager first execution already WAS this update, so nothing is lost either way: raise (default), or fall back
-        to eager execution for the rest of the run when the caller allowed it."""
-        import sys
-        torch.cuda.synchronize()
-        if not self.allow_eager_fallback:
-            raise RuntimeError(f"hipGraph capture of the {what} failed ({e}); pass allow_eager_fallback=True (or "
-                               f"use_graphs=False) to run eagerly") from e
-        print(f"[gank] hipGraph capture of the {what} failed ({e}); running eagerly", file=sys.stderr)
-        self.use_graphs = False
+                seg.append(g)
+            self._graphs['g_seg'] = seg
+        except Exception as e:  # noqa: BLE001
+            graphs.capture_failed('the bucketed generator update', e, self.allow_eager_fallback)
+            self.use_graphs = False
 
     def _agree_on_capture(self):
         """A rank whose capture of a collective failed replays graph / eager collective / graph while the others would replay
@@ -770,12 +719,46 @@ class SNGANTrainer:
             _dist.all_reduce(flag, op=_dist.ReduceOp.MIN, group=self.pg)
             self.capture_collectives = bool(int(flag.item()))
 
+    def _capture_whole(self, what, update):
+        """update() -- a whole update, under data parallel with its collectives -- as ONE graph, or None: the caller takes the
+        split form (graphs with the collectives issued eagerly between them).  A capture that fails on a collective says so and
+        clears `capture_collectives`; the ranks then agree (every rank enters with the same setting, so every rank calls
+        this), and a rank that did capture drops its graph when another could not."""
+        g = None
+        try:
+            with graphs.capture() as g:
+                update()
+        except Exception as e:  # noqa: BLE001
+            if not self.dp:
+                raise
+            g = None
+            torch.cuda.synchronize()
+            print(f"[gank] capturing the {what} with its collectives as one graph failed ({e}); the collectives stay between "
+                  f"graphs", file=sys.stderr)
+            self.capture_collectives = False
+        if self.dp:
+            self._agree_on_capture()
+            if not self.capture_collectives:
+                return None
+        return g
+
     def _allreduce(self, flat):
         if self.dp:
             parallel.allreduce_sum_(flat["grads"], self.pg, self.grad_wire_dtype, single_rank_too=True)
 
     def _run(self, key, fwd_bwd, opt, flat):
-        """fwd+bwd (graph) -> [RCCL all-reduce] -> Adam (graph)."""
+        """fwd+bwd (graph) -> [RCCL all-reduce] -> Adam (graph).  The first call of a key runs eagerly on a side stream (this IS
+        the step: allocator warm-up, lazy init) and captures the same code in the same call (capture executes nothing); later
+        calls replay."""
+        if self.use_graphs and key in self._graphs:
+            g1, g2 = self._graphs[key]
+            self._ensure_clean(flat)
+            self._ensure_sn_state()
+            g1.replay()
+            if g2 is not None:
+                self._allreduce(flat)
+                g2.replay()
+            return
         # critic updates outside data parallel: the spectral norm's backward apply rides on the optimiser launch (FUSE_SN_TAIL)
         defer = opt if (FUSE_SN_TAIL and opt is self.d_opt and not self.dp and self.sn_state is not None) else None
         fwd_bwd_plain = fwd_bwd
@@ -783,86 +766,44 @@ class SNGANTrainer:
         def fwd_bwd():
             with Fn.defer_sn_apply(defer):
                 return fwd_bwd_plain()
-        if not self.use_graphs:
+
+        def update():
             fwd_bwd()
             self._allreduce(flat)
             opt.apply()
+        if not self.use_graphs:
+            update()
             return
-        if key not in self._graphs:
-            # the first call of each update runs eagerly on a side stream (this IS the step: allocator
-            # warm-up, lazy init), then the same code is captured (capture executes nothing)
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                fwd_bwd()
-                self._allreduce(flat)
-                opt.apply()
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            try:
-                # thread_local: the RCCL watchdog thread polls events concurrently under data parallel
-                whole = not self.dp or self.capture_collectives
-                if whole:
-                    try:
-                        g1 = torch.cuda.CUDAGraph()
-                        with _capture(g1):       # forward + backward [+ RCCL all-reduce] + optimiser: ONE graph
-                            fwd_bwd()
-                            self._allreduce(flat)
-                            opt.apply()
-                        self._graphs[key] = (g1, None)
-                    except Exception as e:  # noqa: BLE001
-                        if not self.dp:
-                            raise
-                        import sys
-                        torch.cuda.synchronize()
-                        print(f"[gank] capturing the all-reduce inside the {key!r} update graph failed ({e}); "
-                              f"the collective stays between two graphs", file=sys.stderr)
-                        self.capture_collectives = False
-                    if self.dp:
-                        self._agree_on_capture()    # (entered with the same setting on every rank, so every rank calls this)
-                    if key in self._graphs:
-                        if not self.dp or self.capture_collectives:
-                            return
-                        del self._graphs[key]       # another rank fell back: every rank takes the split form
-                g1 = torch.cuda.CUDAGraph()
-                with _capture(g1):
+        graphs.eager_on_side_stream(update)
+        try:
+            # forward + backward [+ RCCL all-reduce] + optimiser: ONE graph
+            g1 = self._capture_whole(f'{key!r} update', update) if (not self.dp or self.capture_collectives) else None
+            g2 = None
+            if g1 is None:
+                with graphs.capture() as g1:
                     fwd_bwd()
-                g2 = torch.cuda.CUDAGraph()
-                with _capture(g2):
+                with graphs.capture() as g2:
                     opt.apply()
-                self._graphs[key] = (g1, g2)
-            except Exception as e:  # noqa: BLE001
-                self._capture_failed(f'{key!r} update', e)
-            return
-        g1, g2 = self._graphs[key]
-        self._ensure_clean(flat)
-        self._ensure_sn_state()
-        g1.replay()
-        if g2 is not None:
-            self._allreduce(flat)
-            g2.replay()
+            self._graphs[key] = (g1, g2)
+        except Exception as e:  # noqa: BLE001
+            graphs.capture_failed(f'the {key!r} update', e, self.allow_eager_fallback)
+            self.use_graphs = False
 
     def _run_plain(self, key, fn):
-        """Capture-and-replay of a forward-only piece (no optimiser, no exchange)."""
+        """Capture-and-replay of a forward-only piece (no optimiser, no exchange), by the protocol of _run."""
         if not self.use_graphs:
             fn()
-            return
-        if key not in self._graphs:
-            st = torch.cuda.Stream()
-            st.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(st):
-                fn()
-            torch.cuda.current_stream().wait_stream(st)
-            torch.cuda.synchronize()
+        elif key in self._graphs:
+            self._graphs[key][0].replay()
+        else:
+            graphs.eager_on_side_stream(fn)
             try:
-                g = torch.cuda.CUDAGraph()
-                with _capture(g):
+                with graphs.capture() as g:
                     fn()
                 self._graphs[key] = (g, None)
             except Exception as e:  # noqa: BLE001
-                self._capture_failed(repr(key), e)
-            return
-        self._graphs[key][0].replay()
+                graphs.capture_failed(repr(key), e, self.allow_eager_fallback)
+                self.use_graphs = False
 
     # ---- public API ---------------------------------------------------------------------------------
     def d_step(self, real_u8, labels):

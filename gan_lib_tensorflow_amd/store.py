@@ -157,6 +157,14 @@ class ParamStore:
             g.zero_()
 
 
+def adam_state(flat, lr, beta1, beta2, world):
+    """Device-resident state of tf.train.AdamOptimizer over one flatten() buffer, as kernels.adam_tf reads it: the
+    hyper-parameters `hp` (gradients are averaged over the ranks: 1/world) and the step count `t`."""
+    dev = flat["params"].device
+    return dict(hp=torch.tensor([lr, beta1, beta2, 1e-8, 1.0 / world, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev),
+                t=torch.zeros(1, dtype=torch.int64, device=dev), flat=flat)
+
+
 _default_store = None
 
 

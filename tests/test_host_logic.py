@@ -116,3 +116,26 @@ def test_sampling_quantisation_and_inception_score_statistics():
     assert len(seen) == 2 and all(lo >= -1 and hi <= 1 and sh == (64, 4, 4, 3) for lo, hi, sh in seen) and abs(m - 1.0) < 1e-12
     with pytest.raises(NotImplementedError):
         get_inception_score(imgs)
+
+
+def test_capture_failure_policy_raises_unless_eager_fallback_is_allowed(monkeypatch, capsys):
+    """graphs.capture_failed, the one failure policy of every capture site: synchronise, then RuntimeError naming both ways out
+    (chained to the cause), or -- with the fallback allowed -- a message on stderr and a plain return.  No device is needed:
+    the synchronise is counted, and a GraphRunner with graphs disabled just calls through."""
+    from gan_lib_tensorflow_amd import graphs
+    syncs = []
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda: syncs.append(1))
+    cause = ValueError("boom")
+    with pytest.raises(RuntimeError, match=r"hipGraph capture of 'd' failed \(boom\)") as ei:
+        graphs.capture_failed(repr('d'), cause, False)
+    assert "allow_eager_fallback=True" in str(ei.value) and "use_graphs=False" in str(ei.value) and ei.value.__cause__ is cause
+    assert len(syncs) == 1 and capsys.readouterr().err == ""
+    assert graphs.capture_failed("the 'g' update", cause, True) is None
+    assert len(syncs) == 2
+    err = capsys.readouterr().err
+    assert "hipGraph capture of the 'g' update failed (boom)" in err and "running eagerly" in err
+    runner = graphs.GraphRunner(enabled=False)
+    assert not runner.enabled and runner.run('k', lambda: 7) == 7 and runner.run('k', lambda: 8) == 8 and not runner.graphs
+    calls = []
+    runner.update('k', lambda: calls.append('fwd_bwd'), lambda: calls.append('apply'), None, None, 1)
+    assert calls == ['fwd_bwd', 'apply']
