@@ -235,6 +235,10 @@ PROTOTYPES = {
     "gank_debug_tr_probe": [P, P],
     "gank_msssim_level": [P, P, I, I, I, I, I, I, C.POINTER(C.c_float), F, F, F, P, P, P, P],
     "gank_msssim_level_parts": [I, I, I, I],
+    "gank_pix2pix_load_examples": [P, I, I, I, I, I, I, I, I, P, P, P, I, P],
+    "gank_rgb_to_lab": [P, P, L, P],
+    "gank_lab_to_rgb": [P, P, L, P],
+    "gank_pix2pix_convert_u8": [P, P, I, L, I, I, I, I, P, P],
 }
 _RET = {"gank_last_error": C.c_char_p, "gank_sn_ws_floats": C.c_long, "gank_cbn_bwd_ws_floats": C.c_long, "gank_label_conv3x3_bwd_ws_floats": C.c_long, "gank_conv2d_wgrad_ws_elems": C.c_long, "gank_convpool3x3_wgrad_ws_elems": C.c_long, "gank_upconv3x3_wgrad_ws_elems": C.c_long, "gank_conv2d_wgrad_batched_ws_elems": C.c_long, "gank_conv2d_wgrad_slab_elems": C.c_long, "gank_prof_calibrate": C.c_double, "gank_prof_bytes": C.c_double}
 

@@ -1922,3 +1922,79 @@ def prof_bytes(family):
 def prof_calibrate(n=200):
     """average ms an event pair around an empty kernel reads (the fixed cost inside every profiler record)"""
     return float(lib().gank_prof_calibrate(int(n), _stream()))
+
+
+# ------------------------------------------------------------------ Pix2Pix input pipeline (Pix2Pix/train.py)
+PIX_MODES = {"pair": 0, "multiple_A": 1, "lab_colorization": 2}
+PIX_CHANNELS = {0: (3, 3), 1: (6, 3), 2: (1, 2)}      # (A, B) channels per mode
+
+
+def pix2pix_load_examples(raw, table, mode, direction, scale_h, scale_w, crop, inputs=None, targets=None, dtype=None):
+    """gank_pix2pix_load_examples: raw uint8 [N,H,Wraw,3] + int32 [N,3] (flip, offset_y, offset_x) -> (inputs, targets)
+    [N,crop,crop,C] of `dtype` (BF16, the default, or F32), written in place when given.  A table on the host (a NumPy array or
+    a CPU tensor) is checked here -- offsets outside [0, scale - crop] raise -- and uploaded; a device table cannot be read
+    without a synchronisation, so the kernel clamps its rows into that range instead."""
+    n, h, wraw, c3 = raw.shape
+    if not isinstance(table, torch.Tensor):
+        table = torch.as_tensor(table)
+    if not table.is_cuda:
+        if table.dtype != I32 or tuple(table.shape) != (n, 3):
+            raise RuntimeError(f"gank: pix2pix_load_examples: the table must be int32 [{n}, 3], got {table.dtype} {tuple(table.shape)}")
+        for axis, name, scale in ((1, "offset_y", scale_h), (2, "offset_x", scale_w)):
+            lo, hi = int(table[:, axis].min()), int(table[:, axis].max())
+            if lo < 0 or hi > scale - crop:
+                raise RuntimeError(f"gank: pix2pix_load_examples: {name} in [{lo}, {hi}] is outside [0, scale - crop] = [0, {scale - crop}]")
+        table = table.to(raw.device)
+    if c3 != 3 or raw.dtype != torch.uint8:
+        raise RuntimeError(f"gank: pix2pix_load_examples takes uint8 [N,H,W,3] frames, got {raw.dtype} {tuple(raw.shape)}")
+    ca, cb = PIX_CHANNELS[mode] if direction == 0 else PIX_CHANNELS[mode][::-1]
+    dtype = dtype or (inputs.dtype if inputs is not None else BF16)
+    if dtype not in (BF16, F32):
+        raise RuntimeError(f"gank: pix2pix_load_examples writes {BF16} or float32, not {dtype}")
+    if inputs is None:
+        inputs = torch.empty((n, crop, crop, ca), dtype=dtype, device=raw.device)
+    if targets is None:
+        targets = torch.empty((n, crop, crop, cb), dtype=dtype, device=raw.device)
+    if tuple(inputs.shape) != (n, crop, crop, ca) or tuple(targets.shape) != (n, crop, crop, cb) or tuple(table.shape) != (n, 3):
+        raise RuntimeError(f"gank: pix2pix_load_examples: inputs {tuple(inputs.shape)} / targets {tuple(targets.shape)} / table {tuple(table.shape)} "
+                           f"do not fit {n} frames, crop {crop}, channels {ca} + {cb}")
+    _lib.check(lib().gank_pix2pix_load_examples(_p(raw, torch.uint8, "raw"), n, h, wraw, mode, direction, scale_h, scale_w, crop, _p(table, I32, "table"),
+                                                _p(inputs, dtype, "inputs"), _p(targets, dtype, "targets"), 0 if dtype == BF16 else 1, _stream()),
+               "pix2pix_load_examples")
+    return inputs, targets
+
+
+def _lab_map(fn, name, x):
+    if x.shape[-1] != 3:
+        raise RuntimeError(f"gank: {name}: image must have 3 color channels, got {tuple(x.shape)}")
+    y = torch.empty_like(x)
+    _lib.check(fn(_p(x, F32, "image"), _p(y), x.numel() // 3, _stream()), name)
+    return y
+
+
+def rgb_to_lab(srgb):
+    """gank_rgb_to_lab: fp32 [...,3] sRGB in [0,1] -> CIE Lab"""
+    return _lab_map(lib().gank_rgb_to_lab, "rgb_to_lab", srgb)
+
+
+def lab_to_rgb(lab):
+    """gank_lab_to_rgb: fp32 [...,3] CIE Lab -> sRGB in [0,1]"""
+    return _lab_map(lib().gank_lab_to_rgb, "lab_to_rgb", lab)
+
+
+def pix2pix_convert_u8(x, brightness=None, c0=0, cw=None, deprocess=True):
+    """gank_pix2pix_convert_u8: x [...,C] in [-1,1] (BF16 or fp32) -> uint8 [...,cw] of channels c0..c0+cw-1; with
+    `brightness` [...,1], x is the 2-channel ab tensor and the result is the uint8 RGB of augment().  deprocess=False: x is in [0,1]."""
+    c = x.shape[-1]
+    if x.dtype not in (BF16, F32):
+        raise RuntimeError(f"gank: pix2pix_convert_u8 takes {BF16} or float32, got {x.dtype}")
+    if brightness is not None:
+        if brightness.dtype != x.dtype or brightness.shape[:-1] != x.shape[:-1] or brightness.shape[-1] != 1:
+            raise RuntimeError(f"gank: pix2pix_convert_u8: brightness {brightness.dtype} {tuple(brightness.shape)} does not fit ab {x.dtype} {tuple(x.shape)}")
+        cw = 3
+    elif cw is None:
+        cw = c - c0
+    out = torch.empty(tuple(x.shape[:-1]) + (cw,), dtype=torch.uint8, device=x.device)
+    _lib.check(lib().gank_pix2pix_convert_u8(_p(x, None, "image"), _p(brightness, None, "brightness"), 0 if x.dtype == BF16 else 1, x.numel() // c, c, c0,
+                                             cw, 1 if deprocess else 0, _p(out), _stream()), "pix2pix_convert_u8")
+    return out

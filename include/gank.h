@@ -876,6 +876,33 @@ int gank_msssim_level(const void* img1, const void* img2, int dtype, int N, int 
                       float c1, float c2, float offset, float* part, float* pool1, float* pool2, void* stream);
 int gank_msssim_level_parts(int H, int W, int C, int size);
 
+/* ---- Pix2Pix input pipeline (Pix2Pix/train.py of the reference) --------------------------------------------------------
+ * gank_pix2pix_load_examples: load_examples (train.py:355-431) for a batch, one launch.  raw: uint8 [N,H,Wraw,3] on the
+ *   device, 4-byte aligned.  mode 0: pair, A | B of Wraw/2 columns (:395-396); 1: multiple_A, three panels of Wraw/3, A = the
+ *   channels of panel 0 then panel 1 (6 channels), B = panel 2 (:376-391); 2: lab_colorization, A = L/50-1 (1 channel),
+ *   B = (a/110, b/110) of the whole frame (:364-369).  direction 0 = AtoB (inputs = A, targets = B), 1 = BtoA (:398-403).
+ *   Order: x/255 (:355); split and x*2-1, or rgb_to_lab + preprocess_lab, per source pixel; horizontal flip (:411);
+ *   ResizeMethod.AREA to [scale_h, scale_w] (:415: output y covers [y*s, (y+1)*s), s = in/out; a source row weighs the length
+ *   of its overlap with that span; the sum is divided by s_y*s_x); crop x crop at (offset_y, offset_x) (:417-420).
+ *   table: int32 [N][3] on the device, (flip, offset_y, offset_x) per image, shared by input and target (:405); the host
+ *   cannot see it, so the kernel clamps the offsets into [0, scale - crop] (callers check their host copy).
+ *   inputs [N,crop,crop,Ca], targets [N,crop,crop,Cb] (NHWC; the channel counts above, swapped for BtoA); out_dtype 0 = the
+ *   library's 16-bit activation type (gank_act_dtype), 1 = float32.  fp32 arithmetic, one rounding at the store.
+ *   Refused: null pointers, unknown codes, Wraw not divisible by the panel count, scale < crop (:421-422).
+ * gank_rgb_to_lab / gank_lab_to_rgb: train.py:178-218 / :221-262 on fp32 [pixels][3], constants, masks and clip unchanged.
+ * gank_pix2pix_convert_u8: deprocess + convert_image_dtype(uint8, saturate=True) (:141-144, :633):
+ *   out = trunc(clamp((x+1)/2 * 255.5, 0, 255)).  x: [pixels][C], in_dtype 0 = 16-bit activation type, 1 = float32;
+ *   deprocess = 0 skips the (x+1)/2 for an image that is in [0,1] already (convert alone).
+ *   brightness == NULL: out uint8 [pixels][Cw] = channels c0 .. c0+Cw-1 of x (c0 = C/2 = Cw: the tf.split(...)[1] of :650-652).
+ *   brightness != NULL ([pixels][1], same dtype): augment (:265-271) -- x is the 2-channel ab tensor (C = 2, c0 = 0, Cw = 3),
+ *   out uint8 [pixels][3] = convert(lab_to_rgb(deprocess_lab(brightness, a, b))) in the same launch. */
+int gank_pix2pix_load_examples(const void* raw, int N, int H, int Wraw, int mode, int direction, int scale_h, int scale_w, int crop,
+                               const int* table, void* inputs, void* targets, int out_dtype, void* stream);
+int gank_rgb_to_lab(const float* srgb, float* lab, long pixels, void* stream);
+int gank_lab_to_rgb(const float* lab, float* srgb, long pixels, void* stream);
+int gank_pix2pix_convert_u8(const void* x, const void* brightness, int in_dtype, long pixels, int C, int c0, int Cw, int deprocess,
+                            void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
