@@ -425,14 +425,25 @@ __device__ __forceinline__ void rng_finish(unsigned long long* state, unsigned l
   }
 }
 
+// Box-Muller on the four words of one Philox call: (x, y) -> r1 cos(2 pi u2), r1 sin(2 pi u2) and (z, w) -> the second pair, with
+// u1 = 1 - u01(x) in (0,1] and u2 = u01(y).  The angle goes to sincospif as 2 * u2 (exact): its reduction is exact, so a draw next to a
+// zero of the sine or cosine keeps its relative accuracy; the product 6.2831853f * u2 is rounded BEFORE the reduction and left
+// |z| < 1e-4 wrong by up to 1e-7 absolute -- tens of bf16 ulps (found by tests/test_rng_gpu.py against the float64 reference)
+__device__ __forceinline__ void box_muller(const u4& r, float z[4]) {
+  const float ra = sqrtf(-2.f * logf(1.f - u01(r.x))), rb = sqrtf(-2.f * logf(1.f - u01(r.z)));
+  float sa, ca, sb, cb;
+  sincospif(2.f * u01(r.y), &sa, &ca);
+  sincospif(2.f * u01(r.w), &sb, &cb);
+  z[0] = ra * ca; z[1] = ra * sa; z[2] = rb * cb; z[3] = rb * sb;
+}
+
 __global__ void rng_normal_kernel(bf16* __restrict__ y, long n, unsigned long long* __restrict__ state, unsigned* __restrict__ done) {
   const unsigned long long seed = state[0], off = state[1];
   const long n4 = (n + 3) >> 2;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     const u4 r = philox4x32_10((unsigned long long)i, off, seed);
-    const float u1 = 1.f - u01(r.x), u2 = u01(r.y), u3 = 1.f - u01(r.z), u4_ = u01(r.w);  // (0,1]
-    const float ra = sqrtf(-2.f * logf(u1)), rb = sqrtf(-2.f * logf(u3));
-    const float z[4] = {ra * cosf(6.2831853f * u2), ra * sinf(6.2831853f * u2), rb * cosf(6.2831853f * u4_), rb * sinf(6.2831853f * u4_)};
+    float z[4];
+    box_muller(r, z);
     for (int e = 0; e < 4; e++)
       if (i * 4 + e < n) y[i * 4 + e] = f2bf(z[e]);
   }
@@ -478,9 +489,8 @@ __global__ void generator_feed_kernel(int* __restrict__ labels, long n_lab, int 
     const long n4 = (n + 3) >> 2;
     for (long i = (b - bl) * (long)blockDim.x + threadIdx.x; i < n4; i += (long)bn * blockDim.x) {
       const u4 r = philox4x32_10((unsigned long long)i, off, seed);
-      const float u1 = 1.f - u01(r.x), u2 = u01(r.y), u3 = 1.f - u01(r.z), u4_ = u01(r.w);  // (0,1]
-      const float ra = sqrtf(-2.f * logf(u1)), rb = sqrtf(-2.f * logf(u3));
-      const float z[4] = {ra * cosf(6.2831853f * u2), ra * sinf(6.2831853f * u2), rb * cosf(6.2831853f * u4_), rb * sinf(6.2831853f * u4_)};
+      float z[4];
+      box_muller(r, z);
       for (int e = 0; e < 4; e++)
         if (i * 4 + e < n) y[i * 4 + e] = f2bf(z[e]);
     }

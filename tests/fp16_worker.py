@@ -211,6 +211,29 @@ def _adam_guard():
     assert int(opt.health[0]) == len(bad), opt.health.tolist()
 
 
+@section("device RNG against the host Philox reference")
+def _rng():
+    """rng_normal at n = 1027 against the float64 Box-Muller of tests/philox_ref.py: |got - ref64| <= 2^-11 |ref64| + 1e-5 (half an ulp
+    of IEEE half, and the slack of the float32 log / sqrt / sin / cos); preprocess_real bit for bit under the half rounding.
+    Measured on an MI355X: max(|got - ref64| - 2^-11 |ref64|) = -1.1e-7 (never beyond half an ulp)."""
+    import philox_ref as P
+    seed, off, n = 0x1234_5678_9ABC, 3, 1027
+    st = torch.tensor([seed, off], dtype=torch.int64, device="cuda")
+    z = K.rng_normal((n,), st)
+    assert z.dtype == torch.float16
+    ref = P.normal64(n, seed, off)
+    got = z.to(torch.float64).cpu().numpy()
+    slack = float((np.abs(got - ref) - 2.0 ** -11 * np.abs(ref)).max())
+    print(f"rng_normal (half) n={n}: max(|got-ref64| - 2^-11|ref64|) = {slack:.3e}", flush=True)
+    assert np.isfinite(got).all() and slack <= 1e-5, slack
+    data = torch.randint(0, 256, (3, 3072), generator=torch.Generator().manual_seed(3), dtype=torch.uint8)
+    y = K.preprocess_real(data.cuda(), st)
+    want = P.fp16_bits(P.preprocess(data.numpy(), seed, off + 1, rounding=P.fp16_round).reshape(-1)).view(np.int16)
+    assert torch.equal(y.reshape(-1).view(torch.int16).cpu(), torch.from_numpy(want))
+    assert st.tolist() == [seed, off + 2]
+    return f"normal slack {slack:.3e}"
+
+
 # ---- the headline batch (64 = two towers of 32; generator update on 2 x 64 fakes) with the STATIC LOSS SCALE (default 1024 for
 # this build): generator gradients against the float64 oracle at 0.25 / 0.30 / 0.29 / 0.31 of the bfloat16 build's limits
 # (tests/test_model_gpu.py::test_headline_batch_64...: 0.02 / 0.10 / 0.13 / 0.22 relative L2 by depth; measured here 0.0006 /

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SECTIONS = ["conv two-group", "conv patch", "conv generic 8x8", "conv 1x1", "conv narrow input", "upconv phase form",
             "wgrad all-taps", "cond_batchnorm", "SNGAN critic loss + gradients", "SNGAN generator loss + gradients",
             "SNGAN training iterations under hipGraph replay", "Adam skips non-finite gradients",
-            "SNGAN batch-64 generator gradients, loss scale 1024"]
+            "device RNG against the host Philox reference", "SNGAN batch-64 generator gradients, loss scale 1024"]
 
 
 @pytest.fixture(scope="module")
