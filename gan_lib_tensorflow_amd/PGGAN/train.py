@@ -7,7 +7,8 @@ One step (train.py:185-193) = 1 generator update + n_dis = 5 critic updates at f
     gen loss    : -mean(D(G(z)))                                           (:107)       (D(fake) runs with NO_OPS, :102)
 both with tf.train.AdamOptimizer(1e-4, beta1=0, beta2=0.9)               (:130-134).
 `args` is any object with the reference's flag names (batch_size, image_size, block_count, trans, inputs_norm, z_dim, n_dis,
-max_iter).  Data parallel: flat gradient buffers, one RCCL all-reduce per update, 1/world inside the Adam kernel.
+max_iter, model).  `model` = 'nvidia' (model_nvidia.py) | 'resnet' (model_resnet.py, the reference's default; the generator's
+batch-norm moving statistics are non-trainable state and stay out of the optimiser's buffers).  Data parallel: flat gradient buffers, one RCCL all-reduce per update, 1/world inside the Adam kernel.
 """
 import types
 
@@ -18,7 +19,17 @@ from .. import kernels as K
 from .. import parallel
 from ..graphs import GraphRunner
 from ..store import ParamStore, adam_state, set_default_store
-from .model_nvidia import PGGAN
+
+
+def model_class(name):
+    """the `--model` switch of train.py:62-67"""
+    if name == 'nvidia':
+        from .model_nvidia import PGGAN
+    elif name == 'resnet':
+        from .model_resnet import PGGAN
+    else:
+        raise NotImplementedError('Not supported model!')
+    return PGGAN
 
 
 def default_args(**over):
@@ -41,7 +52,7 @@ class PGGANTrainer:
             import torch.distributed as dist
             self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
         self.rng_state = K.new_rng_state(parallel.data_seed(seed, self.rank), self.device)
-        self.model = PGGAN(args)
+        self.model = model_class(args.model)(args)
         self.step = 0
         with torch.no_grad():            # build once: variables are created by name on first use
             z = torch.zeros((args.batch_size, args.z_dim), dtype=K.BF16, device=self.device)

@@ -211,6 +211,8 @@ PROTOTYPES = {
     "gank_minibatch_std_fwd": [P, P, P, I, I, I, P],
     "gank_minibatch_std_bwd": [P, P, P, P, I, I, I, P],
     "gank_resize_bilinear": [P, P, I, I, I, I, I, I, P],
+    "gank_resize_nearest_fwd": [P, P, I, I, I, I, I, I, P],
+    "gank_resize_nearest_bwd": [P, P, I, I, I, I, I, I, P],
     "gank_concat_channels": [P, P, P, L, I, I, P],
     "gank_pool2d": [P, P, I, I, I, I, I, I, I, I, I, I, I, I, P],
     "gank_relu_to_channels": [P, P, L, I, I, I, P],

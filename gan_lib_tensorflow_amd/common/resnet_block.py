@@ -1,5 +1,5 @@
-"""Block library -- drop-in for common/resnet_block.py:24-184 and the private copy inside
-SNGAN/gan_cifar_resnet.py:80-234 of the reference.
+"""Block library -- drop-in for common/resnet_block.py:24-349 and the private copy inside
+SNGAN/gan_cifar_resnet.py:80-234 of the reference (the PGGAN builders of :187-349 are at the end of the file).
 
 Same functions, signatures and variable names.  What differs is underneath: every resampling /
 activation / shortcut-add around a convolution is folded into the MFMA conv kernel's gather or
@@ -10,15 +10,19 @@ epilogue instead of being a TensorFlow op that materialises a tensor:
   pre-activation relu = relu on the conv operand (D) or fused into the CBN apply kernel (G);
   shortcut + output   = residual add in the conv epilogue.
 """
+import contextlib
 import functools
 
 import torch
 
 from .. import functional as Fn
+from .. import functional2 as F2
 from .. import kernels as K
 from ..store import get_default_store
 from .ops import conv2d as _conv2d
+from .ops import linear as _linear
 from .ops import normalization as _normalization
+from .ops import sn as _sn
 
 # reference globals (common/resnet_block.py:20-21; SNGAN/gan_cifar_resnet.py:43-44,51-52 overrides them)
 NORMALIZATION_G = True
@@ -273,3 +277,101 @@ def OptimizedResBlockDisc1(inputs, spectral_normed=False, update_collection=None
     return conv_2(inputs=output, filter_size=3, name='D.Block.1.Conv2',
                   spectral_normed=spectral_normed, update_collection=update_collection,
                   he_init=True, biases=biases, in_relu=True, residual=shortcut)
+
+
+# ######## ######## PGGAN ######## ######## #   (common/resnet_block.py:187-349)
+def get_dim(stage):
+    """(:188-189) `min(2048 / 2**stage, 512)`: a float under Python 3, the channel counts are its integer values; get_dim(-1) = 512"""
+    return int(min(2048 / (2 ** stage), 512))
+
+
+@contextlib.contextmanager
+def _pggan_normalize_rules():
+    """Normalize as common/resnet_block.py:32-50 resolves it for the PGGAN builders: `labels` is None everywhere, so every `G.`
+    layer is the unconditional train-mode batch norm (:46-48); every critic block passes spectral_normed=True, so every `D.` layer
+    is the identity (:34-36).  This module's flags carry the SNGAN script's settings (it overrides them, and so may a caller); they
+    are pinned to that resolution for the duration of a builder and restored."""
+    global NORMALIZATION_G, NORMALIZATION_D, CONDITIONAL, ACGAN
+    saved = (NORMALIZATION_G, NORMALIZATION_D, CONDITIONAL, ACGAN)
+    NORMALIZATION_G, NORMALIZATION_D, CONDITIONAL, ACGAN = True, False, False, False
+    try:
+        yield
+    finally:
+        NORMALIZATION_G, NORMALIZATION_D, CONDITIONAL, ACGAN = saved
+
+
+def _pggan_check(bc, trans, inputs_norm, labels):
+    if trans and bc == 0:
+        raise ValueError('trans=True needs block_count >= 1: the fade-in branch of the reference graph asks for G.UpBlock.0 / D.DownBlock.0')
+    if inputs_norm:
+        raise NotImplementedError('inputs_norm is outside the paths this library runs (common/ops/conv2d.py)')
+    if labels is not None:
+        raise NotImplementedError('the PGGAN model passes no labels (PGGAN/model_resnet.py:35,66)')
+
+
+def Generator_PGGAN(noise, bc, trans=False, alpha=0.01, inputs_norm=False, labels=None, training=True):
+    """(:192-263) noise [N, z_dim] -> images [N, 4 * 2**bc, 4 * 2**bc, 3], tanh range.  bc: count of up blocks; trans: the newest block
+    fades in with weight alpha (a Python float or an fp32[1] device tensor)."""
+    _pggan_check(bc, trans, inputs_norm, labels)
+    with _pggan_normalize_rules():
+        # (N, 4, 4, 1024)
+        output = _linear.Linear(noise, noise.shape[-1], 4 * 4 * 1024, 'G.Input', inputs_norm=inputs_norm, biases=True, initialization=None)
+        output = output.reshape(-1, 4, 4, 1024)
+        output = Normalize('G.N0', output, labels=labels, relu=True)                # + nonlinearity (:212-213)
+        output = _conv2d.Conv2D(output, output.shape[-1], 1024, 3, 1, 'G.Conv', he_init=True, biases=True)
+        for i in range(bc - 1):
+            output = ResidualBlock(output, output.shape[-1], get_dim(i), 3, 'G.UpBlock.{}'.format(i + 1), inputs_norm=inputs_norm,
+                                   resample='up', labels=labels)
+        if trans:
+            out_a, out_b = Fn.fork(output)
+            toRGB1 = ResidualBlock(out_a, out_a.shape[-1], get_dim(bc - 1), 3, 'G.UpBlock.{}'.format(bc), inputs_norm=inputs_norm,
+                                   resample='up', labels=labels)
+            toRGB1 = ResidualBlock(toRGB1, toRGB1.shape[-1], get_dim(bc - 1), 3, 'G.{}_toRGB1'.format(bc), inputs_norm=inputs_norm,
+                                   resample=None, labels=labels)
+            # skip connection: the previous resolution's features, resized to the new one, through their own block (:235-238)
+            toRGB2 = Fn.resize_nearest(out_b, (toRGB1.shape[1], toRGB1.shape[2]))
+            toRGB2 = ResidualBlock(toRGB2, toRGB2.shape[-1], get_dim(bc - 1), 3, 'G.{}_toRGB2'.format(bc), inputs_norm=inputs_norm,
+                                   resample=None, labels=labels)
+            toRGB = Fn.blend(toRGB2, toRGB1, alpha)                                  # fade in (:241)
+        else:
+            if bc > 0:
+                toRGB = ResidualBlock(output, output.shape[-1], get_dim(bc - 1), 3, 'G.UpBlock.{}'.format(bc), inputs_norm=inputs_norm,
+                                      resample='up', labels=labels)
+            else:
+                toRGB = output
+            toRGB = ResidualBlock(toRGB, toRGB.shape[-1], get_dim(bc - 1), 3, 'G.{}_toRGB'.format(bc), inputs_norm=inputs_norm,
+                                  resample=None, labels=labels)
+        output = Normalize('G.Output_Normalize', toRGB, labels=labels, relu=True)   # + nonlinearity (:255-256)
+        return _conv2d.Conv2D(output, output.shape[-1], 3, 3, 1, 'G.Output', he_init=False, out_tanh=True)     # + tanh (:257-261)
+
+
+def Discriminator_PGGAN(x_var, c_var, bc, trans=False, alpha=0.01, inputs_norm=False, labels=None,
+                        update_collection=None, reuse=False):
+    """(:266-349) x_var [N, 4 * 2**bc, 4 * 2**bc, 3] -> logits [N].  The fromRGB layers are residual blocks on the image: their
+    main branch sees relu(image) (N1 is the identity and the nonlinearity still runs, :130-131), their 1x1 shortcut the raw image.
+    All spectral norms of the pass are one batched launch group (common.ops.sn.precomputed)."""
+    _pggan_check(bc, trans, inputs_norm, labels)
+    store = get_default_store()
+    prefix = store.full_name('')[:-1]
+    kw = dict(spectral_normed=True, update_collection=update_collection, inputs_norm=inputs_norm, biases=True)
+    with _pggan_normalize_rules(), _sn.precomputed(store, prefix, update_collection):
+        if trans:
+            x_a, x_b = Fn.fork(x_var)
+            fromRGB1 = ResidualBlock(x_a, 3, get_dim(bc - 1), 3, 'D.{}_fromRGB1'.format(bc), resample=None, **kw)
+            fromRGB1 = ResidualBlock(fromRGB1, get_dim(bc - 1), get_dim(bc - 1), 3, 'D.DownBlock.{}'.format(bc), resample='down', **kw)
+            # skip connection: the image resized to the previous resolution (out[h, w] = in[2h, 2w]) through its own block (:296-302)
+            fromRGB2 = Fn.resize_nearest(x_b, (fromRGB1.shape[1], fromRGB1.shape[2]))
+            fromRGB2 = ResidualBlock(fromRGB2, 3, get_dim(bc - 1), 3, 'D.{}_fromRGB2'.format(bc), resample=None, **kw)
+            x_code = Fn.blend(fromRGB2, fromRGB1, alpha)                             # (:305)
+        else:
+            x_code = ResidualBlock(x_var, 3, get_dim(bc - 1), 3, 'D.{}_fromRGB'.format(bc), resample=None, **kw)
+            if bc > 0:
+                x_code = ResidualBlock(x_code, get_dim(bc - 1), get_dim(bc - 1), 3, 'D.DownBlock.{}'.format(bc), resample='down', **kw)
+        for i in range(1, bc):
+            x_code = ResidualBlock(x_code, x_code.shape[-1], get_dim(bc - 1 - i), 3, 'D.DownBlock.{}'.format(bc - i), resample='down', **kw)
+        output = ResidualBlock(x_code, x_code.shape[-1], get_dim(0), 3, 'D.NoneBlock', resample=None, **kw)
+        output = nonlinearity(output, activation_fn='relu')
+        output = F2.mean_hw(output)                                                  # tf.reduce_mean(output, axis=[1, 2])
+        logits = _linear.Linear(output, output.shape[-1], 1, 'D.Output', spectral_normed=True, update_collection=update_collection,
+                                inputs_norm=inputs_norm, biases=True, initialization=None)
+    return logits.reshape(-1)

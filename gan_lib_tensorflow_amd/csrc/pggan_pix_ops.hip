@@ -145,6 +145,96 @@ extern "C" int gank_resize_bilinear(const void* x, void* y, int N, int Hi, int W
   return 0;
 }
 
+// ---- tf.image.resize_nearest_neighbor(align_corners=False), TF 1.5: src = min(floor(dst * (in / out)), in - 1), the scale in fp32 --
+// (common/resnet_block.py:236 doubles the features of the fading-in generator branch, :297 halves the critic's image: out[h, w] =
+// in[2h, 2w], the top-left pixel of each 2x2 cell).  Forward: a gather.  Backward: one lane per SOURCE element (or 8 channels of it)
+// sums in fp32 the gradients of the destination pixels that map to it and rounds once; a source no destination maps to stores 0.
+__device__ __forceinline__ int rnn_src(int o, float scale, int in) {
+  const int s = (int)floorf((float)o * scale);
+  return s < in - 1 ? s : in - 1;
+}
+// first destination index whose source is >= s (rnn_src is non-decreasing in o; `out` when there is none): the quotient is only a
+// first guess, the two loops settle it with rnn_src itself
+__device__ __forceinline__ int rnn_first_dst(int s, float scale, int in, int out) {
+  int o = (int)floorf((float)s / scale);
+  o = o < 0 ? 0 : (o > out ? out : o);
+  while (o > 0 && rnn_src(o - 1, scale, in) >= s) o--;
+  while (o < out && rnn_src(o, scale, in) < s) o++;
+  return o;
+}
+// T = one element (bf16) or eight (u32x4); Cg = channels / elements per T
+template <typename T>
+__global__ void resize_nearest_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, long total, int Hi, int Wi, int Ho, int Wo, int Cg) {
+  const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % Cg);
+    long t = i / Cg;
+    const int ox = (int)(t % Wo); t /= Wo;
+    const int oy = (int)(t % Ho);
+    const long n = t / Ho;
+    y[i] = x[((n * Hi + rnn_src(oy, sy, Hi)) * Wi + rnn_src(ox, sx, Wi)) * Cg + c];
+  }
+}
+template <int V>
+__global__ void resize_nearest_bwd_kernel(const bf16* __restrict__ dy, bf16* __restrict__ dx, long total, int Hi, int Wi, int Ho, int Wo, int Cg) {
+  const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % Cg);
+    long t = i / Cg;
+    const int ix = (int)(t % Wi); t /= Wi;
+    const int iy = (int)(t % Hi);
+    const long n = t / Hi;
+    const int oy0 = rnn_first_dst(iy, sy, Hi, Ho), ox0 = rnn_first_dst(ix, sx, Wi, Wo);
+    float acc[V];
+#pragma unroll
+    for (int e = 0; e < V; e++) acc[e] = 0.f;
+    for (int oy = oy0; oy < Ho && rnn_src(oy, sy, Hi) == iy; oy++)
+      for (int ox = ox0; ox < Wo && rnn_src(ox, sx, Wi) == ix; ox++) {
+        const bf16* g = dy + (((n * Ho + oy) * Wo + ox) * Cg + c) * V;
+        if constexpr (V == 8) {
+          const bf16x8 v = *reinterpret_cast<const bf16x8*>(g);
+#pragma unroll
+          for (int e = 0; e < 8; e++) acc[e] += bf2f(v[e]);
+        } else {
+          acc[0] += bf2f(g[0]);
+        }
+      }
+    if constexpr (V == 8) {
+      bf16x8 o;
+#pragma unroll
+      for (int e = 0; e < 8; e++) o[e] = f2bf(acc[e]);
+      *reinterpret_cast<bf16x8*>(dx + i * 8) = o;
+    } else {
+      dx[i] = f2bf(acc[0]);
+    }
+  }
+}
+extern "C" int gank_resize_nearest_fwd(const void* x, void* y, int N, int Hi, int Wi, int Ho, int Wo, int C, void* stream) {
+  GANK_REQUIRE(x && y && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0, "resize_nearest_fwd: bad arguments");
+  if (C % 8 == 0) {
+    const long total = (long)N * Ho * Wo * (C / 8);
+    hipLaunchKernelGGL(resize_nearest_fwd_kernel<u32x4>, g1(total, 2048), dim3(256), 0, (hipStream_t)stream, (const u32x4*)x, (u32x4*)y, total, Hi, Wi, Ho, Wo, C / 8);
+  } else {
+    const long total = (long)N * Ho * Wo * C;
+    hipLaunchKernelGGL(resize_nearest_fwd_kernel<bf16>, g1(total, 2048), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)y, total, Hi, Wi, Ho, Wo, C);
+  }
+  GANK_LAUNCH_OK("resize_nearest_fwd");
+  return 0;
+}
+// dy [N,Ho,Wo,C] -> dx [N,Hi,Wi,C] (every element written: no fill in front, no atomics)
+extern "C" int gank_resize_nearest_bwd(const void* dy, void* dx, int N, int Hi, int Wi, int Ho, int Wo, int C, void* stream) {
+  GANK_REQUIRE(dy && dx && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0, "resize_nearest_bwd: bad arguments");
+  if (C % 8 == 0) {
+    const long total = (long)N * Hi * Wi * (C / 8);
+    hipLaunchKernelGGL(resize_nearest_bwd_kernel<8>, g1(total, 2048), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy, (bf16*)dx, total, Hi, Wi, Ho, Wo, C / 8);
+  } else {
+    const long total = (long)N * Hi * Wi * C;
+    hipLaunchKernelGGL(resize_nearest_bwd_kernel<1>, g1(total, 2048), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy, (bf16*)dx, total, Hi, Wi, Ho, Wo, C);
+  }
+  GANK_LAUNCH_OK("resize_nearest_bwd");
+  return 0;
+}
+
 // ---- channel concat / split of NHWC tensors --------------------------------------------------------------------------
 __global__ void concat_c_kernel(const bf16* __restrict__ a, const bf16* __restrict__ b, bf16* __restrict__ y, long pixels, int Ca, int Cb) {
   const int C = Ca + Cb;

@@ -1692,6 +1692,24 @@ def blend(a, b, alpha):
     return _Blend.apply(a, b, alpha)
 
 
+class _ResizeNearest(Function):
+    """tf.image.resize_nearest_neighbor (TF 1.5, align_corners=False; common/resnet_block.py:236,297)"""
+
+    @staticmethod
+    def forward(ctx, x, out_hw):
+        ctx.in_hw = (x.shape[1], x.shape[2])
+        return K.resize_nearest_fwd(_c(x), out_hw)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return K.resize_nearest_bwd(_c(dy), ctx.in_hw), None
+
+
+def resize_nearest(x, out_hw):
+    """x [N,Hi,Wi,C] -> [N,Ho,Wo,C]: out[y, x] = in[min(floor(y * Hi/Ho), Hi - 1), min(floor(x * Wi/Wo), Wi - 1)]"""
+    return _ResizeNearest.apply(x, (int(out_hw[0]), int(out_hw[1])))
+
+
 class _MinibatchStd(Function):
     @staticmethod
     def forward(ctx, x):

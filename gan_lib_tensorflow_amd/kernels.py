@@ -1755,6 +1755,22 @@ def resize_bilinear(x, out_hw):
     return y
 
 
+def resize_nearest_fwd(x, out_hw):
+    """tf.image.resize_nearest_neighbor (TF 1.5, align_corners=False): x [N,Hi,Wi,C] -> [N,Ho,Wo,C]"""
+    n, hi, wi, c = x.shape
+    y = torch.empty((n, out_hw[0], out_hw[1], c), dtype=BF16, device=x.device)
+    _lib.check(lib().gank_resize_nearest_fwd(_p(x, BF16, "x"), _p(y), n, hi, wi, out_hw[0], out_hw[1], c, _stream()), "resize_nearest_fwd")
+    return y
+
+
+def resize_nearest_bwd(dy, in_hw):
+    """gradient of resize_nearest_fwd: dy [N,Ho,Wo,C] -> dx [N,Hi,Wi,C] (every element written)"""
+    n, ho, wo, c = dy.shape
+    dx = torch.empty((n, in_hw[0], in_hw[1], c), dtype=BF16, device=dy.device)
+    _lib.check(lib().gank_resize_nearest_bwd(_p(dy, BF16, "dy"), _p(dx), n, in_hw[0], in_hw[1], ho, wo, c, _stream()), "resize_nearest_bwd")
+    return dx
+
+
 def pool2d(x, k, stride, pad, out_hw, mode, out=None, c_off=0):
     """mode 'max' | 'avg' (average over the in-image elements); writes channels [c_off, c_off + C) of `out` when given"""
     n, h, w, c = x.shape

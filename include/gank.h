@@ -755,6 +755,13 @@ int gank_blend_dev(const void* a, const void* b, const float* alpha, void* y, lo
 int gank_minibatch_std_fwd(const void* x, void* y, float* ws, int B, int HW, int C, void* stream);
 int gank_minibatch_std_bwd(const void* dy, const void* x, float* ws, void* dx, int B, int HW, int C, void* stream);
 int gank_resize_bilinear(const void* x, void* y, int N, int Hi, int Wi, int Ho, int Wo, int C, void* stream);
+/* resize_nearest: tf.image.resize_nearest_neighbor (TF 1.5, align_corners=False; common/resnet_block.py:236,297 -- the 2x upsampled
+ * features of the fading-in generator branch and the critic's image halved to out[h, w] = in[2h, 2w]): x [N,Hi,Wi,C] -> y [N,Ho,Wo,C],
+ * src = min(floor(dst * (in / out)), in - 1) with the scale in fp32; any positive sizes, 16-byte accesses when C % 8 == 0. */
+int gank_resize_nearest_fwd(const void* x, void* y, int N, int Hi, int Wi, int Ho, int Wo, int C, void* stream);
+/* its gradient (common/resnet_block.py:236,297): dx [N,Hi,Wi,C] = per source element the fp32 sum of the dy [N,Ho,Wo,C] pixels that
+ * read it, rounded once; sources nothing reads get 0.  Writes every element of dx: no fill in front, no atomics. */
+int gank_resize_nearest_bwd(const void* dy, void* dx, int N, int Hi, int Wi, int Ho, int Wo, int C, void* stream);
 int gank_concat_channels(const void* a, const void* b, void* y, long pixels, int Ca, int Cb, void* stream);
 /* ---- Inception-v3 classifier of the Inception-score harness (common/inception/inception_score.py:29-47): its pooling layers
  * and the branch concat.  pool2d: x [N,H,W,C] -> y[..., c_off : c_off + C] of [N,Ho,Wo,Cy]; mode 0 max, 1 average over the
