@@ -16,15 +16,19 @@
 //     ggO = gamma*s/M * (M*a - A0 - (x-mu)*s^2*A1)
 //     gI  = gamma * [ (x-mu)*s^3/M * (A0*G0/M - AG + 3*s^2*G1*A1/M) + A1*s^3/M * (G0/M - dy) + G1*s^3/M * (A0/M - a) ]
 //     gG  = s * (AG - A0*G0/M - s^2*A1*G1/M)
+// a and dy are not centred: with a mean of order one over 2^18 rows, AG and A0*G0/M agree in their leading five digits,
+// and a float running sum of a thousand block partials (atomics, arrival order) alone spent most of the 2e-3 allowed on
+// gG.  So a thread's few rows are summed in float, everything above that (row lanes, blocks) in double, and the two
+// differences that cancel -- AG - A0*G0/M, and x - mean(x) for a and dy -- are formed in double before they become float.
 // ---------------------------------------------------------------------------------------------------------------
-__global__ void bn2_zero_kernel(float* __restrict__ p, int n) {
+__global__ void bn2_zero_kernel(double* __restrict__ p, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = 0.f;
+  if (i < n) p[i] = 0.0;
 }
 
 __global__ __launch_bounds__(256) void bn2_sums_kernel(const bf16* __restrict__ a, const bf16* __restrict__ dy, const bf16* __restrict__ x,
-                                                       const float* __restrict__ stats, float* __restrict__ ws, long rows, int C, long rows_per_block) {
-  // thread = (8-channel group, row lane); ws [5][C] (atomics: a few hundred blocks x C adds)
+                                                       const float* __restrict__ stats, double* __restrict__ ws, long rows, int C, long rows_per_block) {
+  // thread = (8-channel group, row lane); ws [5][C] double (atomics: a few hundred blocks x C adds)
   const int cg = C >> 3, RL = 256 / cg;
   const int g = threadIdx.x % cg, rl = threadIdx.x / cg;
   const long r0 = blockIdx.x * rows_per_block;
@@ -55,18 +59,19 @@ __global__ __launch_bounds__(256) void bn2_sums_kernel(const bf16* __restrict__ 
     for (int e = 0; e < 8; e++) red[threadIdx.x * 8 + e] = s[k][e];
     __syncthreads();
     for (int c = threadIdx.x; c < C; c += 256) {
-      float t = 0.f;
-      for (int l = 0; l < RL; l++) t += red[(l * cg + (c >> 3)) * 8 + (c & 7)];
+      double t = 0.0;
+      for (int l = 0; l < RL; l++) t += (double)red[(l * cg + (c >> 3)) * 8 + (c & 7)];
       atomicAdd(ws + k * C + c, t);
     }
   }
 }
 
 __global__ __launch_bounds__(256) void bn2_apply_kernel(const bf16* __restrict__ a, const bf16* __restrict__ dy, const bf16* __restrict__ x,
-                                                        const float* __restrict__ gamma, const float* __restrict__ stats, const float* __restrict__ ws,
+                                                        const float* __restrict__ gamma, const float* __restrict__ stats, const double* __restrict__ ws,
                                                         bf16* __restrict__ gI, bf16* __restrict__ ggO, float* __restrict__ gG, long rows, int C) {
   const long n8 = rows * (C >> 3);
   const float M = (float)rows;
+  const double invM = 1.0 / (double)rows;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
     const int c0 = (int)(i % (C >> 3)) * 8;
     const bf16x8 va = *reinterpret_cast<const bf16x8*>(a + i * 8);
@@ -77,12 +82,15 @@ __global__ __launch_bounds__(256) void bn2_apply_kernel(const bf16* __restrict__
     for (int e = 0; e < 8; e++) {
       const int c = c0 + e;
       const float mu = stats[c], s = stats[C + c], gm = gamma[c];
-      const float A0 = ws[c], A1 = ws[C + c], G0 = ws[2 * C + c], G1 = ws[3 * C + c], AG = ws[4 * C + c];
+      const double A0 = ws[c], G0 = ws[2 * C + c];
+      const float A1 = (float)ws[C + c], G1 = (float)ws[3 * C + c];
+      const float cov = (float)(ws[4 * C + c] - A0 * G0 * invM);                          // AG - A0*G0/M
       const float fa = bf2f(va[e]), fg = bf2f(vg[e]), d = bf2f(vx[e]) - mu;
+      const float ca = (float)((double)fa - A0 * invM), cg = (float)((double)fg - G0 * invM);   // a - mean(a), dy - mean(dy)
       const float s2 = s * s, s3 = s2 * s;
-      oO[e] = f2bf(gm * s / M * (M * fa - A0 - d * s2 * A1));
-      const float all_sub = A0 * G0 / M - AG + 3.f * s2 * G1 * A1 / M;
-      oI[e] = f2bf(gm * (d * s3 / M * all_sub + A1 * s3 / M * (G0 / M - fg) + G1 * s3 / M * (A0 / M - fa)));
+      oO[e] = f2bf(gm * s * (ca - d * s2 * A1 / M));
+      const float all_sub = 3.f * s2 * G1 * A1 / M - cov;
+      oI[e] = f2bf(gm * (d * s3 / M * all_sub - A1 * s3 / M * cg - G1 * s3 / M * ca));
     }
     *reinterpret_cast<bf16x8*>(gI + i * 8) = oI;
     *reinterpret_cast<bf16x8*>(ggO + i * 8) = oO;
@@ -90,7 +98,7 @@ __global__ __launch_bounds__(256) void bn2_apply_kernel(const bf16* __restrict__
   if (gG && blockIdx.x == 0)
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
       const float s = stats[C + c];
-      gG[c] += s * (ws[4 * C + c] - ws[c] * ws[2 * C + c] / M - s * s * ws[C + c] * ws[3 * C + c] / M);
+      gG[c] += s * ((float)(ws[4 * C + c] - ws[c] * ws[2 * C + c] * invM) - s * s * (float)ws[C + c] * (float)ws[3 * C + c] / M);
     }
 }
 
@@ -99,15 +107,17 @@ extern "C" int gank_bn_bwd_bwd(const void* ggI, const void* dy, const void* x, c
   GANK_REQUIRE(ggI && dy && x && gamma && stats && gI && ggO && ws && rows > 0, "bn_bwd_bwd: null pointer");
   GANK_REQUIRE(C % 8 == 0 && C <= 2048 && 256 % (C / 8) == 0, "bn_bwd_bwd: unsupported channel count %d", C);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn2_zero_kernel, dim3((5 * C + 255) / 256), dim3(256), 0, s, ws, 5 * C);
+  GANK_REQUIRE(((size_t)ws & 7) == 0, "bn_bwd_bwd: ws must be 8-byte aligned (it holds 5*C doubles)");
+  double* wsd = reinterpret_cast<double*>(ws);
+  hipLaunchKernelGGL(bn2_zero_kernel, dim3((5 * C + 255) / 256), dim3(256), 0, s, wsd, 5 * C);
   long blocks = (rows + 255) / 256;
   if (blocks > 1024) blocks = 1024;
   const long rpb = (rows + blocks - 1) / blocks;
   hipLaunchKernelGGL(bn2_sums_kernel, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, (const bf16*)ggI, (const bf16*)dy, (const bf16*)x, stats,
-                     ws, rows, C, rpb);
+                     wsd, rows, C, rpb);
   long ab = (rows * (C / 8) + 255) / 256;
   if (ab > 2048) ab = 2048;
-  hipLaunchKernelGGL(bn2_apply_kernel, dim3((unsigned)ab), dim3(256), 0, s, (const bf16*)ggI, (const bf16*)dy, (const bf16*)x, gamma, stats, ws,
+  hipLaunchKernelGGL(bn2_apply_kernel, dim3((unsigned)ab), dim3(256), 0, s, (const bf16*)ggI, (const bf16*)dy, (const bf16*)x, gamma, stats, wsd,
                      (bf16*)gI, (bf16*)ggO, gG, rows, C);
   GANK_LAUNCH_OK("bn_bwd_bwd");
   return 0;

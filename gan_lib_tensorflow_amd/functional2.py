@@ -12,8 +12,16 @@ written in terms of OTHER Functions of this module, so autograd can differentiat
     pooling: Pool2 <-> Unpool2, SumHW <-> BcastHW (linear, mutually adjoint);
     batch norm (train mode): BNF -> BNB -> gank_bn_bwd_bwd (its second derivative is a kernel of its own).
 
-Weight gradients are RETURNED (autograd accumulates them into `p.grad`, which the trainer points at the flat gradient
-buffer): a filter receives first- and second-order contributions in one backward pass.  Activations bf16 NHWC, weights fp32.
+A filter receives first- and second-order contributions in one backward pass.  Activations bf16 NHWC, weights fp32.
+
+Gradient delivery.  In a backward pass that is itself recorded (create_graph=True) every parameter gradient is RETURNED to
+autograd.  In a pass that is not recorded, a leaf parameter that already owns a contiguous fp32 `.grad` of its own shape (the
+trainer points it at the flat gradient buffer) has its gradient ADDED to that `.grad` by the gradient kernel itself, and
+autograd is handed None for it (`_direct`); a parameter without such a `.grad` has its gradient returned.  A Function cannot
+tell `loss.backward()` from `torch.autograd.grad(loss, params)`, so the same holds for both: a non-recorded
+`torch.autograd.grad` on a parameter that owns a `.grad` ADDS the gradient to that `.grad` and receives None for it
+(an error unless allow_unused=True).  To have gradients returned by `torch.autograd.grad`, clear `.grad` first.
+tests/test_functional2_gpu.py pins each of these modes.
 """
 import torch
 from torch.autograd import Function

@@ -1664,7 +1664,7 @@ def bn_bwd_bwd(ggI, dy, x, gamma, stats, gG=None):
     c = x.shape[-1]
     rows = x.numel() // c
     gI, ggO = torch.empty_like(x), torch.empty_like(x)
-    ws = torch.empty(5 * c, dtype=F32, device=x.device)
+    ws = torch.empty(10 * c, dtype=F32, device=x.device)       # five per-channel sums, accumulated in double
     _lib.check(lib().gank_bn_bwd_bwd(_p(ggI, BF16, "ggI"), _p(dy, BF16, "dy"), _p(x, BF16, "x"), _p(gamma, F32, "gamma"), _p(stats, F32, "stats"),
                                      _p(gI), _p(ggO), _p(gG, F32, "gG"), _p(ws), rows, c, _stream()), "bn_bwd_bwd")
     return gI, ggO

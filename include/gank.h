@@ -723,7 +723,8 @@ int gank_loss_grad_scale(const float* dlogits_f32, const float* g, void* dlogits
  * makes fprop / dgrad / wgrad mutually differentiable); train-mode batch norm needs its own second-order kernel:
  *   gank_bn_bwd_bwd: given ggI = dL/d(dx) of the first backward pass dx = BN'(dy; x, gamma, mean, invstd) over `rows` =
  *   N*H*W rows of C channels (stats = [mean[C], invstd[C]] as gank_cbn_fwd leaves them for one tower, gamma [C]):
- *   gI <- dL/dx, ggO <- dL/d(dy) (bf16 [rows,C]), gG (fp32 [C], may be NULL) += dL/dgamma; ws: fp32 scratch of 5*C.
+ *   gI <- dL/dx, ggO <- dL/d(dy) (bf16 [rows,C]), gG (fp32 [C], may be NULL) += dL/dgamma; ws: scratch of 10*C floats,
+ *   8-byte aligned (the five per-channel sums are accumulated in double).
  *   gank_bn_moving_update: tf.contrib.layers.batch_norm's moving statistics (decay, zero-debiased mean; normalization.py:
  *   10-22) for `groups` towers in one launch; stats [groups][2][C], count = rows per tower (for the unbiased variance).
  *   gank_gp_loss: loss <- lambda * mean_n (sqrt(sum_d g[n,d]^2 + 1e-10) - 1)^2, dgrad <- its derivative (fp32 [N,D]: scaled by
