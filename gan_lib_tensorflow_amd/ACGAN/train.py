@@ -212,3 +212,20 @@ class ACGANTrainer:
             labels = K.rng_labels(self.batch, 10, self.rng_state)
             return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3), labels
         return class_pair_diversity(draw, n_pairs, 10, weights)
+
+    @torch.no_grad()
+    def fid(self, real, n=50000, net=None):
+        """Frechet Inception Distance (common/fid.py) between n samples and `real`: a FeatureMoments, a (mu, sigma) pair, the
+        path of an .npz with `mu` and `sigma`, or images [N,H,W,3].  Samples are the draws of `msssim_diversity` -- batches of
+        `batch_size` on fresh noise and uniform labels, quantised as `((x + 1) * (255.99 / 2))` truncated to uint8 --, mapped back
+        to [-1, 1] and fed to `net.features_f32`; samples and features never leave the device.  net: an `InceptionV3` (the frozen
+        graph's weights are a download)."""
+        from ..common.fid import calculate_fid, sample_moments
+        from ..common.msssim import quantize_on_device
+        set_default_store(self.store)
+
+        def draw():
+            z = K.rng_normal((self.batch, self.z_dim), self.rng_state)
+            labels = K.rng_labels(self.batch, 10, self.rng_state)
+            return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3)
+        return calculate_fid(sample_moments(draw, n, net), real, net)

@@ -927,6 +927,17 @@ class SNGANTrainer:
             return quantize_on_device(self.sample(100, labels)).reshape(-1, 32, 32, 3), labels
         return class_pair_diversity(draw, n_pairs, 10, weights)
 
+    @torch.no_grad()
+    def fid(self, real, n=50000, net=None):
+        """Frechet Inception Distance (the FID column / TODO of the reference's README; common/fid.py) between n samples and
+        `real`: a FeatureMoments, a (mu, sigma) pair, the path of an .npz with `mu` and `sigma`, or images [N,H,W,3].  Samples come
+        through the IS sampling path -- n / 100 calls of `sample(100)` on fresh uniform labels --, are quantised on the device as
+        for the score (:551), mapped back to [-1, 1] and fed to `net.features_f32`; samples and features never leave the device.
+        net: an `InceptionV3` (the frozen graph's weights are a download)."""
+        from ..common.fid import calculate_fid, sample_moments
+        from ..common.msssim import quantize_on_device
+        return calculate_fid(sample_moments(lambda: quantize_on_device(self.sample(100)).reshape(-1, 32, 32, 3), n, net), real, net)
+
 
 def _inception_score_of(trainer, n, classifier, splits, batch_size):
     """(:543-555)  n / 100 calls of `samples_100` -- a Generator(100, ...) pass on fresh uniform labels and fresh noise, batch

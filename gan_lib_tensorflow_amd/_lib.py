@@ -237,6 +237,8 @@ PROTOTYPES = {
     "gank_debug_tr_probe": [P, P],
     "gank_msssim_level": [P, P, I, I, I, I, I, I, C.POINTER(C.c_float), F, F, F, P, P, P, P],
     "gank_msssim_level_parts": [I, I, I, I],
+    "gank_mean_hw_f32": [P, P, I, I, I, P],
+    "gank_moments_update": [P, I, I, I, P, P, P],
     "gank_pix2pix_load_examples": [P, I, I, I, I, I, I, I, I, P, P, P, I, P],
     "gank_rgb_to_lab": [P, P, L, P],
     "gank_lab_to_rgb": [P, P, L, P],

@@ -219,6 +219,52 @@ class InceptionV3:
         return K.pool2d(x, g, 1, 0, (1, 1), 'avg').reshape(x.shape[0], 2048)        # pool_3: 8 x 8 average at 299 x 299
 
     @torch.no_grad()
+    def features_f32(self, images, resize=299):
+        """-> pool_3 features FLOAT32 [N, 2048] for the FID statistics (common/fid.py): the trunk of `features`, kernel for
+        kernel, with the closing average taken by K.mean_hw_f32 -- fp32 accumulation and an fp32 result, where K.pool2d rounds
+        its output to 16 bits.  (`features` is kept as it is: the Inception score's logits are pinned to its bits.)"""
+        x = torch.as_tensor(images)
+        if x.dtype != K.BF16:
+            x = x.to(torch.float32).to(K.BF16)
+        x = x.to(self.device).contiguous()
+        assert x.dim() == 4 and x.shape[3] == 3, tuple(x.shape)
+        if resize and (x.shape[1] != resize or x.shape[2] != resize):
+            x = K.resize_bilinear(x, (resize, resize))
+        x = self._conv(x, 'conv', stride=2, valid=True)
+        x = self._conv(x, 'conv_1', valid=True)
+        x = self._conv(x, 'conv_2')
+        h = (x.shape[1] - 3) // 2 + 1
+        x = K.pool2d(x, 3, 2, 0, (h, h), 'max')
+        x = self._conv(x, 'conv_3', valid=True)
+        x = self._conv(x, 'conv_4', valid=True)
+        h = (x.shape[1] - 3) // 2 + 1
+        x = K.pool2d(x, 3, 2, 0, (h, h), 'max')
+        for nm in ('mixed', 'mixed_1', 'mixed_2'):
+            x = self._b35(x, nm)
+        h = (x.shape[1] - 3) // 2 + 1
+        c = x.shape[3]
+        out = self._new(x, (h, h), 384 + 96 + c)
+        self._conv(x, 'mixed_3/conv', stride=2, valid=True, out=out, c_off=0)
+        t = self._conv(self._conv(x, 'mixed_3/tower/conv'), 'mixed_3/tower/conv_1')
+        self._conv(t, 'mixed_3/tower/conv_2', stride=2, valid=True, out=out, c_off=384)
+        K.pool2d(x, 3, 2, 0, (h, h), 'max', out=out, c_off=480)
+        x = out
+        for nm in ('mixed_4', 'mixed_5', 'mixed_6', 'mixed_7'):
+            x = self._b17(x, nm)
+        h = (x.shape[1] - 3) // 2 + 1
+        c = x.shape[3]
+        out = self._new(x, (h, h), 320 + 192 + c)
+        self._conv(self._conv(x, 'mixed_8/tower/conv'), 'mixed_8/tower/conv_1', stride=2, valid=True, out=out, c_off=0)
+        t = self._conv(x, 'mixed_8/tower_1/conv')
+        t = self._conv(self._conv(t, 'mixed_8/tower_1/conv_1'), 'mixed_8/tower_1/conv_2')
+        self._conv(t, 'mixed_8/tower_1/conv_3', stride=2, valid=True, out=out, c_off=320)
+        K.pool2d(x, 3, 2, 0, (h, h), 'max', out=out, c_off=512)
+        x = out
+        x = self._b8(x, 'mixed_9', 'avg')
+        x = self._b8(x, 'mixed_10', 'max')
+        return K.mean_hw_f32(x)                      # pool_3 in fp32
+
+    @torch.no_grad()
     def logits(self, images, resize=299):
         """-> float32 numpy [N, 1008] (`logits:0`): the callable get_inception_score(classifier=...) expects"""
         f = self.features(images, resize)

@@ -1904,6 +1904,28 @@ def msssim_level(img1, img2, taps, c1, c2, offset, part, pool=True):
     return p1, p2
 
 
+# ------------------------------------------------------------------ FID statistics (common/fid.py)
+def mean_hw_f32(x):
+    """x [n, ..., C] in the 16-bit activation dtype -> float32 [n, C], the mean over the middle axes (gank_mean_hw_f32)"""
+    n, c = x.shape[0], x.shape[-1]
+    hw = x.numel() // (n * c)
+    y = torch.empty((n, c), dtype=F32, device=x.device)
+    _lib.check(lib().gank_mean_hw_f32(_p(x, BF16, "x"), _p(y), n, hw, c, _stream()), "mean_hw_f32")
+    return y
+
+
+def moments_update(x, total, gram):
+    """total float64 [D] += column sums of x [n, D]; gram float64 [D, D] += x^T x on the 16 x 16 tiles on and above the diagonal
+    (gank_moments_update).  x: the 16-bit activation dtype or float32."""
+    if x.dim() != 2 or x.dtype not in (BF16, F32):
+        raise RuntimeError(f"gank: moments_update takes [n, D] features in {BF16} or float32, got {tuple(x.shape)} {x.dtype}")
+    n, d = x.shape
+    if total.numel() != d or gram.numel() != d * d:
+        raise RuntimeError(f"gank: moments_update: sum {tuple(total.shape)} / gram {tuple(gram.shape)} do not fit x {tuple(x.shape)}")
+    _lib.check(lib().gank_moments_update(_p(x, x.dtype, "x"), 0 if x.dtype == BF16 else 1, n, d, _p(total, torch.float64, "sum"),
+                                         _p(gram, torch.float64, "gram"), _stream()), "moments_update")
+
+
 # ------------------------------------------------------------------ profiler
 def prof_enable(on):
     lib().gank_prof_enable(int(on))

@@ -884,6 +884,21 @@ int gank_msssim_level(const void* img1, const void* img2, int dtype, int N, int 
                       float c1, float c2, float offset, float* part, float* pool1, float* pool2, void* stream);
 int gank_msssim_level_parts(int H, int W, int C, int size);
 
+/* ---- Frechet Inception Distance: the statistics stage (common/fid.py; the FID column of the reference README's "Quantitative
+ * evaluation" table and the first entry of its TODO list; pool_3 features as common/inception/inception_score.py:29-47 feeds
+ * them) ------------------------------------------------------------------------------------------------------------------
+ * gank_mean_hw_f32: x [n,HW,C] in the 16-bit activation type -> y FLOAT32 [n,C], the mean over HW: pool_3 without the 16-bit
+ *   rounding of gank_pool2d's output.  fp32 accumulation, one thread per output, the HW addends in index order, no atomics.
+ *   C % 8 == 0, x 16-byte aligned.
+ * gank_moments_update: x [n,D] (dtype 0 = the 16-bit activation type, 1 = float32) is added to the running UNCENTRED
+ *   float64 moments of a feature set: sum [D] += sum_i x[i][.], and gram [D,D] += x^T x on every 16 x 16 tile whose tile row
+ *   <= its tile column; the tiles strictly below the diagonal are neither read nor written (the caller mirrors).  Products
+ *   and sums on v_mfma_f64_16x16x4_f64 (a product of two fp32 values is exact in float64); every tile has one owning wave
+ *   and its sum over i runs in index order: no atomics, no split over i, bit-identical from call to call.  Rows past n in
+ *   the last group of 4 enter as zeros.  n >= 1, D % 16 == 0, 16 <= D <= 4096, x 16-byte aligned. */
+int gank_mean_hw_f32(const void* x, float* y, int n, int HW, int C, void* stream);
+int gank_moments_update(const void* x, int dtype, int n, int D, double* sum, double* gram, void* stream);
+
 /* ---- Pix2Pix input pipeline (Pix2Pix/train.py of the reference) --------------------------------------------------------
  * gank_pix2pix_load_examples: load_examples (train.py:355-431) for a batch, one launch.  raw: uint8 [N,H,Wraw,3] on the
  *   device, 4-byte aligned.  mode 0: pair, A | B of Wraw/2 columns (:395-396); 1: multiple_A, three panels of Wraw/3, A = the
