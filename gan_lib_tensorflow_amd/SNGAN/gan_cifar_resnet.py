@@ -50,6 +50,10 @@ DECAY = True
 N_CRITIC = 5
 CONDITIONAL = True
 ACGAN = False
+# The projection discriminator (Miyato & Koyama) -- the TODO that opens the reference's SNGAN README: "I didn't notice the
+# Projection Discriminator, I plan to add this feature to this repo."  The critic then sees no label in its trunk and outputs
+# D.Output(h) + <E_bar[y], h> on the pooled features h.  Off: the reference's concat conditioning (:276-284).
+PROJECTION = False
 VOCAB_SIZE = 10
 EMBEDDING_DIM = 300
 LOSS_TYPE = 'HINGE'
@@ -159,13 +163,58 @@ FUSED_HEAD = True      # D.Output + hinge loss (+ the layer's three gradients) a
 HEAD_IN_CHAIN = True   # ... and that launch folded into the fused 8x8 chain's forward / backward launches (functional.HingeHeadSpec)
 
 
-def Discriminator(inputs, labels, update_collection=None, reuse=False, loss_head=None):
+def _use_projection(projection):
+    """the `projection` keyword of Discriminator / SNGANTrainer: None = the module constant; it conditions on labels"""
+    projection = PROJECTION if projection is None else bool(projection)
+    if projection and not CONDITIONAL:
+        raise ValueError("projection=True needs CONDITIONAL = True: the projection term is <E[y], h> on the class label")
+    return projection
+
+
+def _projection_critic(store, prefix, inputs, labels, update_collection, loss_head):
+    """The critic of Discriminator(projection=True): the trunk sees no label (D.Block.2 is the generic 128 -> 128 down block, no
+    D.Embedding_y, no concat), the output is D.Output(h) + <E_bar[y], h> on h = reduce_mean(relu(.)) (the reference's pooling, not
+    the paper's sum), E = `Embedding.Label/embedding_map` [VOCAB_SIZE, DIM_D], spectrally normalised with the other eleven weights.
+    loss_head: a functional.ProjectionHeadSpec, called with (h, W_bar, b, E_bar)."""
+    with _sn.precomputed(store, prefix, update_collection, prep_kind=_d_prep_kind, label_dense=None):
+        output = inputs.reshape(-1, 32, 32, 3)
+        output = OptimizedResBlockDisc1(output, spectral_normed=True, update_collection=update_collection, biases=True)
+        output = ResidualBlock(output, DIM_D, DIM_D, 3, 'D.Block.2', spectral_normed=True,
+                               update_collection=update_collection, resample='down', labels=labels, biases=True)
+        if blocks.res_chain8_eligible(output, DIM_D, ['D.Block.3', 'D.Block.4'], labels):
+            output = blocks.ResidualBlockChain8(output, DIM_D, ['D.Block.3', 'D.Block.4'], spectral_normed=True,
+                                                update_collection=update_collection, biases=True, pool=True)
+        else:
+            output = ResidualBlock(output, DIM_D, DIM_D, 3, 'D.Block.3', spectral_normed=True,
+                                   update_collection=update_collection, resample=None, labels=labels, biases=True)
+            output = ResidualBlock(output, DIM_D, DIM_D, 3, 'D.Block.4', spectral_normed=True,
+                                   update_collection=update_collection, resample=None, labels=labels, biases=True)
+            output = Fn.relu_meanpool_hw(output)
+        out_b = None
+        if ACGAN:                            # the auxiliary head reads the forked pooled features (:302-311)
+            output, out_b = Fn.fork(output)
+        w_out, b_out = _linear.linear_variables(DIM_D, 1, 'D.Output', spectral_normed=True, update_collection=update_collection)
+        e_bar = _embedding.normalized_embedding_variable(VOCAB_SIZE, DIM_D, update_collection=update_collection)
+        if ACGAN:
+            output_acgan = _linear.Linear(out_b, DIM_D, 10, 'D.ACGANOutput', spectral_normed=True,
+                                          update_collection=update_collection, biases=True)
+            return Fn.projection_head(output, w_out, b_out, e_bar, labels), output_acgan
+        if loss_head is not None:
+            return loss_head(output, w_out, b_out, e_bar), None
+        return Fn.projection_head(output, w_out, b_out, e_bar, labels), None
+
+
+def Discriminator(inputs, labels, update_collection=None, reuse=False, loss_head=None, projection=None):
     """(:266-313, ACGAN=False)  inputs [n,3072] bf16 (HWC order) -> (logits [n], None).
     loss_head: a callable (features [n, DIM_D], W_bar [DIM_D, 1], b [1]) -> loss that replaces the last dense layer AND the
-    loss on its logits (functional.hinge_d_head / hinge_g_head): the call then returns (loss, None)."""
+    loss on its logits (functional.hinge_d_head / hinge_g_head): the call then returns (loss, None).
+    projection: the projection discriminator instead of the concat conditioning (None: PROJECTION; _projection_critic)."""
+    projection = _use_projection(projection)
     store = get_default_store()
     with store.variable_scope("Discriminator", reuse=reuse):
         prefix = store.full_name('')[:-1]
+        if projection:
+            return _projection_critic(store, prefix, inputs, labels, update_collection, loss_head)
         # the label branch as a per-label table out of the spectral norm's second launch (functional.concat_label)
         label_dense = None
         if LABEL_TABLE:
@@ -300,7 +349,8 @@ class SNGANTrainer:
     losses, :436,:498)."""
 
     def __init__(self, batch_size=BATCH_SIZE, device="cuda", seed=0, use_graphs=True, process_group=None, state=None,
-                 allow_eager_fallback=False, capture_collectives=None, grad_wire_dtype=None, loss_scale=None, loss_type=None, soft_plus=None):
+                 allow_eager_fallback=False, capture_collectives=None, grad_wire_dtype=None, loss_scale=None, loss_type=None, soft_plus=None,
+                 projection=None):
         """allow_eager_fallback: a failed hipGraph capture degrades to eager execution (with a message on stderr) instead of
         raising -- a run that asked for graphs never silently becomes a 10x slower eager run otherwise.
         capture_collectives: under data parallel the RCCL all-reduces are captured INSIDE the update graphs (one graph per
@@ -313,7 +363,9 @@ class SNGANTrainer:
         grad_wire_dtype: 'bf16' sends the gradient buckets over xGMI in the 16-bit activation dtype (half the bytes).
         loss_scale: static loss scale, a power of two (default: 1 for bfloat16 buffers, 1024 for the fp16 build, whose activation
         gradients would otherwise underflow: hinge d loss / d logit is +-1/n and shrinks from there).  The loss nodes multiply
-        d loss / d logits by it, the optimisers divide it out (grad_scale) and count non-finite / zero gradients (`health()`)."""
+        d loss / d logits by it, the optimisers divide it out (grad_scale) and count non-finite / zero gradients (`health()`).
+        projection: this trainer's critic is the projection discriminator (None: PROJECTION)."""
+        self.projection = _use_projection(projection)
         self.device = torch.device(device)
         self.allow_eager_fallback = allow_eager_fallback
         # LOSS_TYPE of the script (:62, SOFT_PLUS = False :63): 'HINGE' (:371-381, :487-492), 'Goodfellow' (-mean(log sigmoid(real)) -
@@ -368,7 +420,7 @@ class SNGANTrainer:
             labels = torch.zeros(b, dtype=torch.int32, device=self.device)
             z = torch.zeros((b, 128), dtype=K.BF16, device=self.device)
             fake = Generator(b, labels, noise=z, groups=N_TOWERS)
-            Discriminator(fake, labels, update_collection=NO_OPS)
+            self._critic(fake, labels, NO_OPS)
         if state is not None:
             self.store.load_state_dict(state)
         self.g_flat = self.store.flatten('Generator')
@@ -492,14 +544,23 @@ class SNGANTrainer:
             flat["grads_all"].zero_()
             flat["clean"] = True
 
+    def _critic(self, x, labels, update_collection, loss_head=None):
+        """Discriminator() of this trainer's kind"""
+        return Discriminator(x, labels, update_collection=update_collection, loss_head=loss_head, projection=self.projection)
+
+    def _hinge_head(self, mode, n_real, labels, out):
+        """the fused last layer + hinge loss of this trainer's kind of critic"""
+        if self.projection:
+            return Fn.ProjectionHeadSpec(mode, n_real, labels, out=out, loss_scale=self.loss_scale)
+        return Fn.HingeHeadSpec(mode, n_real, out=out, loss_scale=self.loss_scale)
+
     # ---- the losses of the script's LOSS_TYPE switch ----------------------------------------------------------
     def _critic_loss(self, both, both_labels, n_real):
         """-> (loss, logits): disc_cost on concat(real, fake) with update_collection=None"""
         if self.loss_type == 'HINGE' and FUSED_HEAD and not self.soft_plus:
-            loss, _ = Discriminator(both, both_labels, update_collection=None,
-                                    loss_head=Fn.HingeHeadSpec(0, n_real, out=self.d_loss, loss_scale=self.loss_scale))
+            loss, _ = self._critic(both, both_labels, None, self._hinge_head(0, n_real, both_labels, self.d_loss))
             return loss, loss.logits
-        logits, _ = Discriminator(both, both_labels, update_collection=None)
+        logits, _ = self._critic(both, both_labels, None)
         if self.soft_plus:               # (:366-367, :372-373, :383-385; softplus(fake) + softplus(-real) IS the sigmoid cross-entropy)
             kind = {'Goodfellow': 5, 'HINGE': 7, 'WGAN': 2}[self.loss_type]
             return Fn.gan_pointwise_loss(logits, n_real, kind, out=self.d_loss), logits
@@ -512,10 +573,9 @@ class SNGANTrainer:
     def _generator_loss(self, fake, fake_labels):
         """-> (loss, logits): gen_cost, critic with update_collection=NO_OPS"""
         if self.loss_type == 'HINGE' and FUSED_HEAD and not self.soft_plus:
-            loss, _ = Discriminator(fake, fake_labels, update_collection=NO_OPS,
-                                    loss_head=Fn.HingeHeadSpec(1, 0, out=self.g_loss, loss_scale=self.loss_scale))
+            loss, _ = self._critic(fake, fake_labels, NO_OPS, self._hinge_head(1, 0, fake_labels, self.g_loss))
             return loss, loss.logits
-        logits, _ = Discriminator(fake, fake_labels, update_collection=NO_OPS)
+        logits, _ = self._critic(fake, fake_labels, NO_OPS)
         if self.soft_plus:               # (:484, :489-490, :494-495)
             return Fn.gan_pointwise_loss(logits, 0, 6 if self.loss_type == 'Goodfellow' else 3, out=self.g_loss), logits
         if self.loss_type in ('HINGE', 'WGAN'):
@@ -879,7 +939,7 @@ class SNGANTrainer:
         real = K.preprocess_real(real_u8.to(self.device), self.rng_state).reshape(b, OUTPUT_DIM) if real_pre is None else real_pre
         both = torch.cat([real, fake], 0)
         both_labels = torch.cat([lab, lab], 0)
-        logits, _ = Discriminator(both, both_labels, update_collection=None)
+        logits, _ = self._critic(both, both_labels, None)
         if self.loss_type == 'WGAN':
             return float(Fn.wgan_d_loss(logits, b))
         if self.loss_type == 'Goodfellow':

@@ -193,6 +193,9 @@ PROTOTYPES = {
     "gank_embedding_bwd": [P, P, P, I, I, I, P],
     "gank_critic_head_hinge": [P, P, P, P, P, P, P, P, I, I, I, I, P],
     "gank_critic_head_hinge_scaled": [P, P, P, P, P, P, P, P, I, I, I, I, F, P],
+    "gank_proj_head_fwd": [P, P, P, P, P, P, I, I, I, P],
+    "gank_proj_head_bwd": [P, P, P, P, P, P, P, P, P, I, I, I, P],
+    "gank_proj_head_hinge_scaled": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, P],
     "gank_hinge_d_loss": [P, P, P, P, I, I, P],
     "gank_gan_pointwise_loss": [P, P, P, P, I, I, I, P],
     "gank_hinge_g_loss": [P, P, P, P, I, P],

@@ -87,11 +87,14 @@ def _trunc_normal(rng, size):
 def sn_pairs(store, prefix, with_names=False):
     """[(W, u)] for every spectrally normalised variable under `prefix`, by the reference's names:
     conv `X/filters/spectral_norm/u` <-> `X/Filters` (conv2d.py:142,170), linear
-    `X/spectral_norm/u` <-> `X/W` (linear.py:140,162-164)."""
+    `X/spectral_norm/u` <-> `X/W` (linear.py:140,162-164), label table `X/embedding_map/spectral_norm/u` <-> `X/embedding_map`
+    (embedding.normalized_embedding_variable; tested before the dense rule, whose suffix it shares)."""
     pairs = []
     for name in store.names(prefix):
         if name.endswith('/filters/spectral_norm/u'):
             wname = name[:-len('/filters/spectral_norm/u')] + '/Filters'
+        elif name.endswith('/embedding_map/spectral_norm/u'):
+            wname = name[:-len('/spectral_norm/u')]
         elif name.endswith('/spectral_norm/u'):
             wname = name[:-len('/spectral_norm/u')] + '/W'
         else:

@@ -1567,6 +1567,90 @@ def hinge_g_head(x, W, bias, out=None, loss_scale=1.0):
     return loss
 
 
+def _proj_targets(ctx, W, bias, E, first):
+    """gradient targets of the projection head's three parameters (inputs `first`, `first` + 1, `first` + 2 of the node) -> (wt, bt,
+    et) for the kernel, `ctx.ret` for autograd (None where the flat gradient buffer was accumulated into)"""
+    tgts, ctx.ret = [], []
+    for j, prm in enumerate((W, bias, E)):
+        tgt = ret = None
+        if prm is not None and ctx.needs_input_grad[first + j]:
+            tgt, acc = _target(prm)
+            ret = None if acc else tgt
+        tgts.append(tgt)
+        ctx.ret.append(ret)
+    return tgts
+
+
+class _ProjectionHead(Function):
+    """The projection discriminator's output (Miyato & Koyama): logits = D.Output(x) + <E_bar[y], x> on the pooled features, one
+    launch each way (kernels.proj_head_fwd / proj_head_bwd) -> logits bf16 [M].  Any loss node may follow."""
+
+    @staticmethod
+    def forward(ctx, x, W, bias, E, labels):
+        ctx.save_for_backward(x, W, E, labels)
+        ctx.bias = bias
+        return K.proj_head_fwd(x, W.detach().reshape(-1), bias.detach() if bias is not None else None, E.detach(), labels)
+
+    @staticmethod
+    def backward(ctx, dl):
+        x, W, E, labels = ctx.saved_tensors
+        wt, bt, et = _proj_targets(ctx, W, ctx.bias, E, 1)
+        dx = K.proj_head_bwd(_c(dl), x, W.detach().reshape(-1), E.detach(), labels, ctx.needs_input_grad[0],
+                             wt.view(-1) if wt is not None else None, bt, et)
+        return (dx, *ctx.ret, None)
+
+
+def projection_head(x, W_bar, b, E_bar, labels):
+    """x bf16 [M, K], W_bar fp32 [K, 1] (the normalised D.Output weight), b fp32 [1] | None, E_bar fp32 [V, K] (the normalised label
+    table), labels int32 [M] -> logits bf16 [M]"""
+    return _ProjectionHead.apply(_c(x), W_bar, b, E_bar, labels)
+
+
+class _ProjHingeHead(Function):
+    """projection_head + hinge loss in one launch (kernels.proj_head_hinge), by the protocol of _HingeHead: the parameter
+    gradients are accumulated by the FORWARD launch, the loss must be differentiated directly with the matching grad_seed."""
+
+    @staticmethod
+    def forward(ctx, x, W, bias, E, labels, n_real, mode, out, loss_scale=1.0):
+        ctx.loss_scale = float(loss_scale)
+        wt, bt, et = _proj_targets(ctx, W, bias, E, 1)
+        for prm, tgt in ((W, wt), (bias, bt), (E, et)):
+            # (see _HingeHead: a forward-only call must not leave the flat gradient buffer marked clean)
+            fl = getattr(prm, "_flat", None) if tgt is not None else None
+            if fl is not None:
+                fl["clean"] = False
+        buf = out.t if out is not None else None
+        loss, logits, dx = K.proj_head_hinge(_c(x), W.detach().reshape(-1), bias.detach() if bias is not None else None, E.detach(), labels,
+                                             n_real, mode, ctx.needs_input_grad[0], wt.view(-1) if wt is not None else None, bt, et, buf,
+                                             loss_scale=ctx.loss_scale)
+        ctx.dx = dx
+        _ProjHingeHead.last_logits = logits
+        return loss.detach() if buf is not None else loss
+
+    @staticmethod
+    def backward(ctx, g):
+        if _seed_scale.get(g.data_ptr()) != ctx.loss_scale:
+            raise NotImplementedError("the fused projection head differentiates the loss itself (loss.backward(gradient=grad_seed(loss, loss_scale)) "
+                                      "with the loss scale its forward launch was given); use projection_head + hinge_*_loss for a weighted sum of losses")
+        return (ctx.dx, *ctx.ret, None, None, None, None, None)
+
+
+class ProjectionHeadSpec:
+    """The projection critic's head + hinge loss as a `loss_head` of Discriminator(projection=True): mode 0 = hinge_d with the first
+    n_real rows real, mode 1 = hinge_g; `labels` int32 [M]; `out`: persistent fp32[1] buffer that receives the loss; loss_scale: see
+    grad_seed.  Called with (features, W_bar, b, E_bar) it is one launch of its own behind the fused 8x8 chain (the chain launches
+    do not carry this head); the logits ride along as `loss.logits`."""
+
+    def __init__(self, mode, n_real=0, labels=None, out=None, loss_scale=1.0):
+        self.mode, self.n_real, self.labels, self.out, self.loss_scale = int(mode), int(n_real), labels, out, float(loss_scale)
+
+    def __call__(self, x, W, bias, E):
+        loss = _ProjHingeHead.apply(x, W, bias, E, self.labels, self.n_real if self.mode == 0 else 0, self.mode,
+                                    _Box(self.out) if self.out is not None else None, self.loss_scale)
+        loss.logits, _ProjHingeHead.last_logits = _ProjHingeHead.last_logits, None
+        return loss
+
+
 class _Box:
     __slots__ = ("t",)
 

@@ -1591,6 +1591,63 @@ def critic_head_hinge(x, w, b, n_real, mode, want_dx=True, w_grad=None, b_grad=N
     return loss, logits, dx
 
 
+def _proj_head_operands(x, w, b, e, labels, **more):
+    """shape and dtype checks of the projection head's operands, before any pointer is taken -> (M, K, V).  more: name ->
+    (tensor | None, dtype, shape)"""
+    if x.dim() != 2:
+        raise ValueError(f"gank: proj_head: x must be [M, K], got {tuple(x.shape)}")
+    m, k = x.shape
+    if e.dim() != 2 or e.shape[1] != k:
+        raise ValueError(f"gank: proj_head: E must be [V, {k}], got {tuple(e.shape)}")
+    v = e.shape[0]
+    checks = dict(x=(x, BF16, (m, k)), w=(w, F32, (k,)), b=(b, F32, (1,)), E=(e, F32, (v, k)), labels=(labels, I32, (m,)), **more)
+    for name, (t, dtype, shape) in checks.items():
+        if t is None:
+            continue
+        if t.numel() != (shape[0] if len(shape) == 1 else shape[0] * shape[1]) or (len(shape) == 2 and tuple(t.shape) != shape):
+            raise ValueError(f"gank: proj_head: {name} must be {list(shape)}, got {tuple(t.shape)}")
+        if t.dtype != dtype:
+            raise RuntimeError(f"gank: {name} must be {dtype}, got {t.dtype}")
+    return m, k, v
+
+
+def proj_head_fwd(x, w, b, e, labels):
+    """projection discriminator head (gank_proj_head_fwd): logits bf16 [M] = x [M,K] (w [K] + E[labels] [V,K]) + b[0]"""
+    m, k, v = _proj_head_operands(x, w, b, e, labels)
+    logits = torch.empty(m, dtype=BF16, device=x.device)
+    _lib.check(lib().gank_proj_head_fwd(_p(x, BF16, "x"), _p(w, F32, "w"), _p(b, F32, "b"), _p(e, F32, "E"), _p(labels, I32, "labels"), _p(logits),
+                                        m, k, v, _stream()), "proj_head_fwd")
+    return logits
+
+
+def proj_head_bwd(dl, x, w, e, labels, want_dx=True, w_grad=None, b_grad=None, e_grad=None):
+    """gank_proj_head_bwd: dx bf16 [M,K] = dl [M] (w + E[labels]) (returned when want_dx); w_grad [K], b_grad [1] and e_grad [V,K]
+    are ACCUMULATED when given (a row of e_grad whose label does not occur is not touched)"""
+    m, k, v = _proj_head_operands(x, w, None, e, labels, dl=(dl, BF16, (x.shape[0],)), w_grad=(w_grad, F32, (x.shape[1],)),
+                                  b_grad=(b_grad, F32, (1,)), e_grad=(e_grad, F32, tuple(e.shape)))
+    dx = torch.empty((m, k), dtype=BF16, device=x.device) if want_dx else None
+    _lib.check(lib().gank_proj_head_bwd(_p(dl, BF16, "dl"), _p(x, BF16, "x"), _p(w, F32, "w"), _p(e, F32, "E"), _p(labels, I32, "labels"), _p(dx),
+                                        _p(w_grad, F32, "w_grad"), _p(b_grad, F32, "b_grad"), _p(e_grad, F32, "e_grad"), m, k, v, _stream()),
+               "proj_head_bwd")
+    return dx
+
+
+def proj_head_hinge(x, w, b, e, labels, n_real, mode, want_dx=True, w_grad=None, b_grad=None, e_grad=None, loss=None, loss_scale=1.0):
+    """projection head + hinge loss + the head's backward pass in one launch (gank_proj_head_hinge_scaled) -> (loss fp32[1], logits
+    bf16 [M], dx bf16 [M,K] | None); mode 0: critic loss with the first n_real rows real, 1: generator loss; w_grad / b_grad / e_grad
+    are ACCUMULATED when given; loss_scale (a power of two) multiplies the gradients, not the loss"""
+    m, k, v = _proj_head_operands(x, w, b, e, labels, w_grad=(w_grad, F32, (x.shape[1],)), b_grad=(b_grad, F32, (1,)),
+                                  e_grad=(e_grad, F32, tuple(e.shape)), loss=(loss, F32, (1,)))
+    loss = torch.empty(1, dtype=F32, device=x.device) if loss is None else loss
+    logits = torch.empty(m, dtype=BF16, device=x.device)
+    dx = torch.empty((m, k), dtype=BF16, device=x.device) if want_dx else None
+    _lib.check(lib().gank_proj_head_hinge_scaled(_p(x, BF16, "x"), _p(w, F32, "w"), _p(b, F32, "b"), _p(e, F32, "E"), _p(labels, I32, "labels"),
+                                                 _p(logits), _p(loss, F32, "loss"), _p(dx), _p(w_grad, F32, "w_grad"), _p(b_grad, F32, "b_grad"),
+                                                 _p(e_grad, F32, "e_grad"), m, k, v, int(n_real), int(mode), float(loss_scale), _stream()),
+               "proj_head_hinge")
+    return loss, logits, dx
+
+
 def softmax_xent(logits, labels):
     n, classes = logits.shape
     loss = torch.empty(1, dtype=F32, device=logits.device)

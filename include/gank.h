@@ -701,6 +701,32 @@ int gank_critic_head_hinge(const void* x, const float* w, const float* b, void* 
  * activation gradients behind this layer; the optimiser divides it out again (hp.grad_scale of gank_adam_tf).  `loss` is unscaled. */
 int gank_critic_head_hinge_scaled(const void* x, const float* w, const float* b, void* logits, float* loss, void* dx, float* w_grad,
                                   float* b_grad, int M, int K, int n_real, int mode, float loss_scale, void* stream);
+/* Projection discriminator head (Miyato & Koyama, "cGANs with Projection Discriminator"; the SNGAN README's open TODO):
+ *   logits[n] = bf16(sum_k x[n][k] * (w[k] + E[y_n][k]) + b[0])
+ * x bf16 [M,K] (the pooled critic features), w fp32 [K] (the normalised D.Output weight), b fp32 [1] or NULL, E fp32 [V,K] (the
+ * normalised label table), labels int32 [M].  A label outside [0, V) is treated as gank_embedding_fwd / _bwd treat it: its
+ * table row reads as zeros (logit = x w + b, dx = dl w) and it contributes to no row of e_grad; nothing is read out of bounds.
+ * Association (all three entry points, exactly): c = w[k] + E[y_n][k] is one fp32 addition; lane l of a 64-lane wave adds the
+ * products x[n][k] * c for k = l, l + 64, ... in increasing k; the 64 lane sums are added by an xor butterfly (offsets 32, 16,
+ * 8, 4, 2, 1); b[0] is added last; the fp32 sum is rounded to 16 bits once.  No fused multiply-add.
+ * Supported: 1 <= M <= 1024, 1 <= K <= 1024, 1 <= V <= 256 (one workgroup; everything lives in 52 KB of LDS); outside, or with a
+ * required pointer NULL, the call returns non-zero and sets gank_last_error().
+ * gank_proj_head_bwd: from an arbitrary upstream dl (bf16 [M]):  dx[n][k] = bf16(dl[n] * (w[k] + E[y_n][k]))  (NULL: skip), and,
+ * ACCUMULATED (NULL: skip):  w_grad[k] += sum_n dl[n] x[n][k];  b_grad[0] += sum_n dl[n];  e_grad[v][k] += sum_{n: y_n = v}
+ * dl[n] x[n][k] -- a row of e_grad whose label does not occur is neither read nor written.  Every sum runs in a fixed order (w_grad:
+ * 8 row slices, each in increasing n, added in slice order; b_grad: lane l sums n = l, l + 64, ..., then the butterfly; e_grad:
+ * increasing n) with no float atomics: two runs give the same bits.  x, w, E, labels and dl are required.
+ * gank_proj_head_hinge_scaled: gank_proj_head_fwd + gank_hinge_d_loss / _g_loss + gank_proj_head_bwd in ONE launch, by the
+ * conventions of gank_critic_head_hinge_scaled (mode 0: critic loss, the first n_real rows real, 0 < n_real < M; mode 1: generator
+ * loss; `loss` unscaled; dl = bf16(loss_scale * d hinge / d logit); the gradients are accumulated by this launch).  Its logits
+ * and dx are bit-identical to the three separate launches; loss, w_grad, b_grad and e_grad sum the same terms. */
+int gank_proj_head_fwd(const void* x, const float* w, const float* b, const float* E, const int32_t* labels, void* logits, int M, int K, int V,
+                       void* stream);
+int gank_proj_head_bwd(const void* dl, const void* x, const float* w, const float* E, const int32_t* labels, void* dx, float* w_grad,
+                       float* b_grad, float* e_grad, int M, int K, int V, void* stream);
+int gank_proj_head_hinge_scaled(const void* x, const float* w, const float* b, const float* E, const int32_t* labels, void* logits, float* loss,
+                                void* dx, float* w_grad, float* b_grad, float* e_grad, int M, int K, int V, int n_real, int mode,
+                                float loss_scale, void* stream);
 /* the other branches of get_loss (common/misc.py:353-394), same conventions (critic kinds: the first n_real logits are real):
  * kind 0 LSGAN critic, 1 LSGAN generator, 2 sigmoid-cross-entropy critic (CGAN / Modified_MiniMax / MiniMax), 3 its
  * non-saturating generator (-log sigmoid(fake): CGAN, Modified_MiniMax), 4 the MiniMax generator (log(1 - sigmoid(fake))).
