@@ -12,22 +12,19 @@ Data parallel (config 3: global batch 256 over 8 GPUs): one process per GPU, eac
 samples and its own batch-norm statistics (as the reference's towers would have); flat gradient buffers summed with one
 RCCL all-reduce per update, 1/world applied inside the Adam kernel.
 """
-import numpy as np
 import torch
 
 from .. import functional as Fn
 from .. import functional2 as F2
 from .. import kernels as K
-from .. import parallel
-from ..graphs import GraphRunner
-from ..store import ParamStore, adam_state, set_default_store
+from .. import trainer
+from ..store import set_default_store
 from .model import ACGAN
 
 
 def polynomial_decay(step, lr0=0.0004, decay_steps=50000, lr_end=0.0002):
-    """tf.train.polynomial_decay(power=1, cycle=False)   (train.py:141)"""
-    s = min(step, decay_steps)
-    return (lr0 - lr_end) * (1.0 - s / float(decay_steps)) + lr_end
+    """tf.train.polynomial_decay(power=1, cycle=False) with the script's values   (train.py:141)"""
+    return trainer.polynomial_decay(step, lr0, decay_steps, lr_end)
 
 
 BATCHED_PREP = True     # operand copies of the weights: one launch per network and update (False: per conv and layout on first use)
@@ -49,18 +46,11 @@ def _g_prep_kind(name, W):
     return 0
 
 
-class ACGANTrainer:
+class ACGANTrainer(trainer.GraphTrainer):
     def __init__(self, batch_size=64, z_dim=128, acgan_scale_G=0.1, n_dis=5, max_iter=100000, device="cuda", seed=0,
                  process_group=None, state=None, use_graphs=True, allow_eager_fallback=False):
-        self.device = torch.device(device)
+        super().__init__(device, seed, process_group, use_graphs, allow_eager_fallback)
         self.batch, self.z_dim, self.scale_g, self.n_dis, self.max_iter = batch_size, z_dim, acgan_scale_G, n_dis, max_iter
-        self.store = set_default_store(ParamStore(self.device, seed=seed))
-        self.pg = process_group
-        self.world, self.rank = 1, 0
-        if process_group is not None:
-            import torch.distributed as dist
-            self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
-        self.rng_state = K.new_rng_state(parallel.data_seed(seed, self.rank), self.device)
         self.model = ACGAN()
         self.global_step = 0
         # build once (variables are created by name on first use)
@@ -69,27 +59,21 @@ class ACGANTrainer:
             z = torch.zeros((batch_size, z_dim), dtype=K.BF16, device=self.device)
             x = self.model.get_generator(z, labels)
             self.model.get_discriminator(x, labels)
-        if state is not None:
-            self.store.load_state_dict(state)
-        self.g_flat = self.store.flatten('g_net')
-        self.d_flat = self.store.flatten('d_net')
-        self.g_params = [self.store.vars[k] for k in self.g_flat['names']]
-        self.d_params = [self.store.vars[k] for k in self.d_flat['names']]
-        for p in self.d_params:
-            p.grad = p.main_grad         # the twice-differentiable critic RETURNS weight gradients: autograd adds them in place here
-            del p.main_grad
-        self.g_opt = adam_state(self.g_flat, 0.0004, 0.0, 0.9, self.world)
-        self.d_opt = adam_state(self.d_flat, 0.0004, 0.0, 0.9, self.world)
+        self._finish_build(state, g_adam=(0.0004, 0.0, 0.9), d_adam=(0.0004, 0.0, 0.9))
         self._g_convs = [(k, v) for k, v in self.store.vars.items() if k.startswith('g_net/') and k.endswith('/Filters') and v.dim() == 4]
         self._refresh_g_prep()
-        self.losses = {}
-        # the two updates as captured hipGraphs (gan_lib_tensorflow_amd/graphs.py): static input buffers, the learning rate
-        # written into the optimiser's device-side hyper-parameters outside the captured region
-        self.graphs = GraphRunner(use_graphs, allow_eager_fallback)     # a failed hipGraph capture raises unless the caller allows eager execution
+        # the static inputs of the captured updates
         self.real_u8 = torch.zeros((batch_size, 3072), dtype=torch.uint8, device=self.device)
         self.real_labels = torch.zeros(batch_size, dtype=torch.int32, device=self.device)
 
+    def _flatten_nets(self, state, g_prefix, d_prefix):
+        super()._flatten_nets(state, g_prefix, d_prefix)
+        for p in self.d_params:
+            p.grad = p.main_grad         # the twice-differentiable critic RETURNS weight gradients: autograd adds them in place here
+            del p.main_grad
+
     def _apply(self, opt):
+        """Adam without the gradient clear (_d_fwd_bwd / _g_fwd_bwd zero the buffers themselves), then the generator's operands"""
         f = opt['flat']
         K.adam_tf(f['params'], f['grads'], f['m'], f['v'], opt['hp'], opt['t'], None)
         if opt is self.g_opt:
@@ -102,10 +86,8 @@ class ACGANTrainer:
         if BATCHED_PREP and self._g_convs:
             K.prep_weights_batched([v for _, v in self._g_convs], want_d=True, kinds=[_g_prep_kind(k, v) for k, v in self._g_convs])
 
-    def _update(self, key, fwd_bwd, opt):
-        """the decayed learning rate, written outside the captured region, then GraphRunner.update"""
-        opt['hp'][0:1].fill_(polynomial_decay(self.global_step, decay_steps=self.max_iter // 2))
-        self.graphs.update(key, fwd_bwd, lambda: self._apply(opt), opt['flat']['grads'], self.pg, self.world)
+    def _learning_rate(self):
+        return polynomial_decay(self.global_step, decay_steps=self.max_iter // 2)
 
     # ---- the two losses (eager; explicit inputs override the device RNG for parity tests) -----------------------------
     def d_loss(self, real, real_labels, z=None, fake_labels=None, alpha=None):
@@ -142,16 +124,11 @@ class ACGANTrainer:
         if fake_labels is None:
             fake_labels = K.rng_labels(b, 10, self.rng_state)
         x_fake = m.get_generator(z, fake_labels)
-        for p in self.d_params:          # g_train_op differentiates w.r.t. g_vars only (train.py:146)
-            p.requires_grad_(False)
-        try:
+        with self.critic_frozen():       # g_train_op differentiates w.r.t. g_vars only (train.py:146)
             disc_fake, ac_fake = m.get_discriminator(x_fake, fake_labels, update_collection='NO_OPS', reuse=True)
             g_gan = Fn.hinge_g_loss(disc_fake)
             g_ac = Fn.softmax_xent(ac_fake, fake_labels)
             total = Fn.weighted_sum([g_gan, g_ac], [1.0, self.scale_g])
-        finally:
-            for p in self.d_params:
-                p.requires_grad_(True)
         self.losses.update(g_loss_gan=g_gan.detach(), g_loss_acgan=g_ac.detach())
         return total
 

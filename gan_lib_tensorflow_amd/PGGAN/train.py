@@ -16,9 +16,8 @@ import torch
 
 from .. import functional as Fn
 from .. import kernels as K
-from .. import parallel
-from ..graphs import GraphRunner
-from ..store import ParamStore, adam_state, set_default_store
+from ..store import set_default_store
+from ..trainer import GraphTrainer
 
 
 def model_class(name):
@@ -40,45 +39,21 @@ def default_args(**over):
     return types.SimpleNamespace(**a)
 
 
-class PGGANTrainer:
+class PGGANTrainer(GraphTrainer):
     def __init__(self, args, device="cuda", seed=0, process_group=None, state=None, use_graphs=True, allow_eager_fallback=False):
         assert args.image_size == 4 * 2 ** args.block_count, "image_size must be 4 * 2**block_count (train.py:52-54)"
+        super().__init__(device, seed, process_group, use_graphs, allow_eager_fallback)
         self.args = args
-        self.device = torch.device(device)
-        self.store = set_default_store(ParamStore(self.device, seed=seed))
-        self.pg = process_group
-        self.world, self.rank = 1, 0
-        if process_group is not None:
-            import torch.distributed as dist
-            self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
-        self.rng_state = K.new_rng_state(parallel.data_seed(seed, self.rank), self.device)
         self.model = model_class(args.model)(args)
         self.step = 0
         with torch.no_grad():            # build once: variables are created by name on first use
             z = torch.zeros((args.batch_size, args.z_dim), dtype=K.BF16, device=self.device)
             x = self.model.get_generator(z, 0.0)
             self.model.get_discriminator(x, 0.0, update_collection='NO_OPS')
-        if state is not None:
-            self.store.load_state_dict(state)
-        self.g_flat = self.store.flatten('g_net')
-        self.d_flat = self.store.flatten('d_net')
-        self.g_params = [self.store.vars[k] for k in self.g_flat['names']]
-        self.d_params = [self.store.vars[k] for k in self.d_flat['names']]
-        self.g_opt = adam_state(self.g_flat, 0.0001, 0.0, 0.9, self.world)
-        self.d_opt = adam_state(self.d_flat, 0.0001, 0.0, 0.9, self.world)
-        self.losses = {}
-        # the two updates as captured hipGraphs: static input rows, the fade-in weight in device memory (written before a replay)
-        self.graphs = GraphRunner(use_graphs, allow_eager_fallback)     # a failed hipGraph capture raises unless the caller allows eager execution
+        self._finish_build(state, g_adam=(0.0001, 0.0, 0.9), d_adam=(0.0001, 0.0, 0.9))
+        # the static inputs of the captured updates: the input rows, the fade-in weight in device memory (written before a replay)
         self.real_u8 = torch.zeros((args.batch_size, args.image_dim), dtype=torch.uint8, device=self.device)
         self.alpha_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
-
-    def _apply(self, opt):
-        f = opt['flat']
-        K.adam_tf(f['params'], f['grads'], f['m'], f['v'], opt['hp'], opt['t'], None, zero_grads=True)
-
-    def _update(self, key, fwd_bwd, opt):
-        """GraphRunner.update: fwd_bwd (graph) -> [RCCL all-reduce] -> Adam (graph)"""
-        self.graphs.update(key, fwd_bwd, lambda: self._apply(opt), opt['flat']['grads'], self.pg, self.world)
 
     def alpha(self, step=None):
         return float(self.step if step is None else step) / float(self.args.max_iter)        # feed_dict alpha (:186)
@@ -113,25 +88,11 @@ class PGGANTrainer:
         if z is None:
             z = K.rng_normal((self.args.batch_size, self.args.z_dim), self.rng_state)
         x_fake = self.model.get_generator(z, alpha, reuse=True)
-        for p in self.d_params:          # g_train_op differentiates w.r.t. g_vars only (:132)
-            p.requires_grad_(False)
-        try:
+        with self.critic_frozen():       # g_train_op differentiates w.r.t. g_vars only (:132)
             disc_fake = self.model.get_discriminator(x_fake, alpha, update_collection='NO_OPS', reuse=True)
-            loss = Fn.hinge_g_loss(disc_fake)
-        finally:
-            for p in self.d_params:
-                p.requires_grad_(True)
-        return loss
+            return Fn.hinge_g_loss(disc_fake)
 
     # ---- updates --------------------------------------------------------------------------------------------------
-    def _backward(self, loss):
-        Fn.reset_deferred()
-        try:
-            loss.backward(gradient=Fn.unit_seed(loss))
-            Fn.join_wgrad()
-        finally:
-            Fn.reset_deferred()
-
     def _d_fwd_bwd(self):
         loss = self.d_loss(self.real_images(self.real_u8), alpha=self.alpha_dev)
         self._backward(loss)

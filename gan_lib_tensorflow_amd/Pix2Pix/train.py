@@ -25,9 +25,8 @@ import torch
 
 from .. import functional as Fn
 from .. import kernels as K
-from .. import parallel
-from ..graphs import GraphRunner
-from ..store import ParamStore, adam_state, set_default_store
+from ..store import set_default_store
+from ..trainer import GraphTrainer, polynomial_decay  # noqa: F401  (polynomial_decay: part of this module's surface)
 from .model import Pix2Pix
 
 
@@ -240,24 +239,12 @@ def append_index(filesets, output_dir, step=False):
     return str(index)
 
 
-def polynomial_decay(step, lr0, decay_steps, lr_end):
-    s = min(step, decay_steps)
-    return (lr0 - lr_end) * (1.0 - s / float(decay_steps)) + lr_end
-
-
-class Pix2PixTrainer:
+class Pix2PixTrainer(GraphTrainer):
     def __init__(self, args, device="cuda", seed=0, process_group=None, state=None, in_channels=3, out_channels=3, use_graphs=True, allow_eager_fallback=False):
         if args.loss_type != 'HINGE':
             raise NotImplementedError('loss_type HINGE (the reference default, train.py:38)')
+        super().__init__(device, seed, process_group, use_graphs, allow_eager_fallback)
         self.args = args
-        self.device = torch.device(device)
-        self.store = set_default_store(ParamStore(self.device, seed=seed))
-        self.pg = process_group
-        self.world, self.rank = 1, 0
-        if process_group is not None:
-            import torch.distributed as dist
-            self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
-        self.rng_state = K.new_rng_state(parallel.data_seed(seed, self.rank), self.device)
         self.model = Pix2Pix()
         self.out_channels = out_channels
         self.global_step = 0
@@ -266,17 +253,9 @@ class Pix2PixTrainer:
             a = torch.zeros((args.batch_size, s, s, in_channels), dtype=K.BF16, device=self.device)
             out = self._generator(a, reuse=False)
             self._critic(a, out, 'NO_OPS', reuse=False)
-        if state is not None:
-            self.store.load_state_dict(state)
-        self.g_flat = self.store.flatten('g_net')
-        self.d_flat = self.store.flatten('d_net')
-        self.g_params = [self.store.vars[k] for k in self.g_flat['names']]
-        self.d_params = [self.store.vars[k] for k in self.d_flat['names']]
-        self.g_opt = adam_state(self.g_flat, args.initial_lr, args.beta1, args.beta2, self.world)
-        self.d_opt = adam_state(self.d_flat, args.initial_lr, args.beta1, args.beta2, self.world)
-        self.losses = {}
-        # the two updates as captured hipGraphs: static input / target buffers, the learning rate written outside the capture
-        self.graphs = GraphRunner(use_graphs, allow_eager_fallback)     # a failed hipGraph capture raises unless the caller allows eager execution
+        adam = (args.initial_lr, args.beta1, args.beta2)
+        self._finish_build(state, g_adam=adam, d_adam=adam)
+        # the static inputs of the captured updates
         self.inputs = torch.zeros((args.batch_size, args.crop_size, args.crop_size, in_channels), dtype=K.BF16, device=self.device)
         self.targets = torch.zeros((args.batch_size, args.crop_size, args.crop_size, out_channels), dtype=K.BF16, device=self.device)
 
@@ -291,15 +270,9 @@ class Pix2PixTrainer:
                                             conv_type=a.conv_type, channel_multiplier=a.channel_multiplier, padding='VALID',
                                             net_type=a.net_type, reuse=reuse)
 
-    def _apply(self, opt):
-        f = opt['flat']
-        K.adam_tf(f['params'], f['grads'], f['m'], f['v'], opt['hp'], opt['t'], None, zero_grads=True)
-
-    def _update(self, key, fwd_bwd, opt):
-        """the decayed learning rate, written outside the captured region, then GraphRunner.update"""
+    def _learning_rate(self):
         a = self.args
-        opt['hp'][0:1].fill_(polynomial_decay(self.global_step, a.initial_lr, a.max_steps, a.end_lr))
-        self.graphs.update(key, fwd_bwd, lambda: self._apply(opt), opt['flat']['grads'], self.pg, self.world)
+        return polynomial_decay(self.global_step, a.initial_lr, a.max_steps, a.end_lr)
 
     # ---- losses ---------------------------------------------------------------------------------------------------
     def d_loss(self, inputs, targets):
@@ -317,29 +290,16 @@ class Pix2PixTrainer:
         generator update's graph contains BOTH critic passes with update_collection=None (:452-475), so `u` advances twice."""
         set_default_store(self.store)
         outputs, outputs_l1 = Fn.fork(self._generator(inputs))     # read by the critic and by the L1 term: one add launch backward
-        for p in self.d_params:
-            p.requires_grad_(False)
-        try:
+        with self.critic_frozen():
             with torch.no_grad():
                 self._critic(inputs, targets, None)            # predict_real: only its u update is observable here
             predict_fake = self._critic(inputs, outputs, None)
             gan = Fn.hinge_g_loss(predict_fake.reshape(-1))
             l1 = Fn.l1_loss(outputs_l1, targets)
-        finally:
-            for p in self.d_params:
-                p.requires_grad_(True)
         self.losses.update(gen_loss_GAN=gan.detach(), gen_loss_L1=l1.detach())
         return Fn.weighted_sum([gan, l1], [self.args.gan_weight, self.args.l1_weight])
 
     # ---- updates --------------------------------------------------------------------------------------------------
-    def _backward(self, loss):
-        Fn.reset_deferred()
-        try:
-            loss.backward(gradient=Fn.unit_seed(loss))
-            Fn.join_wgrad()
-        finally:
-            Fn.reset_deferred()
-
     def _d_fwd_bwd(self):
         loss = self.d_loss(self.inputs, self.targets)
         self._backward(loss)

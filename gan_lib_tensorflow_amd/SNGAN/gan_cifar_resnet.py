@@ -380,11 +380,7 @@ class SNGANTrainer:
         self.batch = batch_size
         self.store = set_default_store(ParamStore(self.device, seed=seed))
         self.pg = process_group
-        self.world = 1
-        self.rank = 0
-        if process_group is not None:
-            import torch.distributed as dist
-            self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
+        self.world, self.rank = parallel.world_and_rank(process_group)
         self.use_graphs = use_graphs
         if loss_scale is None:
             loss_scale = 1024.0 if K.BF16 is torch.float16 else 1.0

@@ -8,7 +8,8 @@ What a captured piece may depend on: device memory at fixed addresses only -- in
 counters / learning rates / fade-in weights / RNG state live on the device and are updated OUTSIDE the captured region.
 
 Three primitives -- `eager_on_side_stream`, `capture`, `capture_failed` -- and two protocols built on them:
-  * `GraphRunner` (ACGAN, PGGAN, Pix2Pix): first call of a key eager, second call capture + one replay, later calls replay;
+  * `GraphRunner` (owned by `trainer.GraphTrainer`, the base of the ACGAN, PGGAN and Pix2Pix trainers, whose `_update` is its
+    only caller): first call of a key eager, second call capture + one replay, later calls replay;
   * `SNGANTrainer` (SNGAN/gan_cifar_resnet.py): first call eager AND captured (nothing replayed), later calls replay; its
     updates may hold their collectives, and the ranks agree on that.
 The two differ in which call consumes RNG state and advances Adam's step count, so they stay apart.

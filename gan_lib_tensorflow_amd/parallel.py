@@ -59,6 +59,13 @@ def allreduce_sum_(flat_grads, group=None, wire_dtype=None, single_rank_too=Fals
     return flat_grads
 
 
+def world_and_rank(process_group):
+    """(world size, rank) of a trainer's process group; (1, 0) without one"""
+    if process_group is None:
+        return 1, 0
+    return dist.get_world_size(process_group), dist.get_rank(process_group)
+
+
 def data_seed(base_seed, rank):
     """Parameter init uses `base_seed` on every rank (identical replicas without a broadcast);
     the data-side RNG (z, fake labels, dequantisation) must differ per rank."""

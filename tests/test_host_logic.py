@@ -139,3 +139,36 @@ def test_capture_failure_policy_raises_unless_eager_fallback_is_allowed(monkeypa
     calls = []
     runner.update('k', lambda: calls.append('fwd_bwd'), lambda: calls.append('apply'), None, None, 1)
     assert calls == ['fwd_bwd', 'apply']
+
+
+def test_critic_frozen_restores_requires_grad_after_the_body_and_after_an_exception():
+    """trainer.GraphTrainer.critic_frozen on plain CPU tensors: no gradient flags inside the body, all back on after it, and
+    after a body that raises (the exception passes through)."""
+    from gan_lib_tensorflow_amd.trainer import GraphTrainer
+    tr = GraphTrainer.__new__(GraphTrainer)        # the context manager reads d_params only
+    tr.d_params = [torch.zeros(3, requires_grad=True), torch.zeros(2, 2, requires_grad=True)]
+    with tr.critic_frozen():
+        assert [p.requires_grad for p in tr.d_params] == [False, False]
+    assert [p.requires_grad for p in tr.d_params] == [True, True]
+    with pytest.raises(ValueError, match="boom"):
+        with tr.critic_frozen():
+            assert not any(p.requires_grad for p in tr.d_params)
+            raise ValueError("boom")
+    assert [p.requires_grad for p in tr.d_params] == [True, True]
+
+
+def test_shared_polynomial_decay_and_its_two_module_level_names():
+    """One formula (trainer.polynomial_decay); ACGAN.train supplies its script's defaults, Pix2Pix.train re-exports it."""
+    from gan_lib_tensorflow_amd import trainer
+    from gan_lib_tensorflow_amd.ACGAN.train import polynomial_decay as acgan_decay
+    from gan_lib_tensorflow_amd.Pix2Pix.train import polynomial_decay as pix_decay
+    assert acgan_decay(0) == 0.0004 and abs(acgan_decay(25000) - 0.0003) < 1e-12 and acgan_decay(10 ** 6) == 0.0002
+    assert trainer.polynomial_decay(0, 0.0004, 50000, 0.0002) == 0.0004 and trainer.polynomial_decay(10 ** 6, 0.0004, 50000, 0.0002) == 0.0002
+    assert abs(trainer.polynomial_decay(25000, 0.0004, 50000, 0.0002) - 0.0003) < 1e-12
+    assert pix_decay is trainer.polynomial_decay
+    assert pix_decay(0, 2e-4, 1000, 1e-4) == 2e-4 and abs(pix_decay(500, 2e-4, 1000, 1e-4) - 1.5e-4) < 1e-12
+
+
+def test_world_and_rank_without_a_process_group():
+    from gan_lib_tensorflow_amd import parallel
+    assert parallel.world_and_rank(None) == (1, 0)
