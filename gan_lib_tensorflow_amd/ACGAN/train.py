@@ -206,3 +206,21 @@ class ACGANTrainer(trainer.GraphTrainer):
             labels = K.rng_labels(self.batch, 10, self.rng_state)
             return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3)
         return calculate_fid(sample_moments(draw, n, net), real, net)
+
+    @torch.no_grad()
+    def inception_score(self, n=50000, net=None, splits=10):
+        """get_inception_score(n) of the training script (train.py:159-171, every evaluation_interval steps, :208-211): n / 100
+        generator passes of 100 samples on fresh normal noise and fresh uniform labels, quantised as
+        `((x + 1) * (255.99 / 2))` truncated to integers, then the Inception score in `splits` splits -> (mean, std).  On the device
+        throughout (common/inception/inception_score.py): quantisation, the map back to [-1, 1], `net.logits_device` and the
+        float64 statistics; only their final state comes back.  net: an `InceptionV3` (the frozen graph's weights are a
+        download)."""
+        from ..common.inception.inception_score import sample_inception_score
+        from ..common.msssim import quantize_on_device
+        set_default_store(self.store)
+
+        def draw():
+            z = K.rng_normal((100, self.z_dim), self.rng_state)
+            labels = K.rng_labels(100, 10, self.rng_state)
+            return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3)
+        return sample_inception_score(draw, int(n / 100), 100, net, splits)

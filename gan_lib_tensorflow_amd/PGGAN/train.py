@@ -130,3 +130,17 @@ class PGGANTrainer(GraphTrainer):
         if z is None:
             z = K.rng_normal((n, self.args.z_dim), self.rng_state)
         return self.model.get_generator(z, self.alpha() if alpha is None else alpha, reuse=True)
+
+    @torch.no_grad()
+    def inception_score(self, n=50000, net=None, splits=10, alpha=None):
+        """get_inception_score(n, alpha) of the training script (:150-162, every evaluation_interval steps at the step's fade-in
+        weight, :195-198): n / 100 generator passes of 100 samples on fresh noise at `alpha` (default: the current one), at the
+        stage's image_size -- the classifier's own bilinear resize takes them to 299 x 299 --, quantised as
+        `((x + 1) * (255.99 / 2))` truncated to integers, then the Inception score in `splits` splits -> (mean, std).  On the device
+        throughout (common/inception/inception_score.py); only the final state of the statistics comes back.  net: an
+        `InceptionV3` (the frozen graph's weights are a download)."""
+        from ..common.inception.inception_score import sample_inception_score
+        from ..common.msssim import quantize_on_device
+        size = self.args.image_size
+        return sample_inception_score(lambda: quantize_on_device(self.sample(100, alpha=alpha)).reshape(-1, size, size, 3), int(n / 100), 100,
+                                      net, splits)

@@ -947,18 +947,30 @@ class SNGANTrainer:
         costs = [self.dev_disc_cost(torch.as_tensor(x), torch.as_tensor(np.asarray(y))) for x, y in dev_batches]
         return float(np.mean(costs)) if costs else float('nan')
 
-    def inception_score(self, n=50000, classifier=None, splits=10, batch_size=100):
+    def inception_score(self, n=50000, classifier=None, splits=10, batch_size=100, net=None):
         """get_inception_score(n) of the training script (:546-555): 50 000 samples every INCEPTION_FREQUENCY iterations
-        (:634-637, `maybe_inception_score`).  classifier: images [-1, 1] NHWC float32 -> logits [b, >= 1000], e.g.
-        `common.inception.inception_v3.InceptionV3.from_npz(path).logits` (the frozen graph's weights are a download)."""
+        (:634-637, `maybe_inception_score`).  Either of
+        classifier: images [-1, 1] NHWC float32 -> logits [b, >= 1000], e.g. `InceptionV3.from_npz(path).logits` (the frozen
+            graph's weights are a download): the reference's host path -- samples to the host, quantised there, softmax and
+            `preds2score` in NumPy;
+        net: an `InceptionV3`: the same n / 100 calls of `sample(100)`, the same draws in the same order, quantised on the
+            device, mapped back to [-1, 1] as `fid` maps them, `net.logits_device` -> `InceptionScore`
+            (common/inception/inception_score.py): samples, logits and probabilities never leave the device."""
+        if net is not None:
+            if classifier is not None:
+                raise ValueError("inception_score: pass classifier= (the host path) or net= (the device path), not both")
+            from ..common.inception.inception_score import sample_inception_score
+            from ..common.msssim import quantize_on_device
+            return sample_inception_score(lambda: quantize_on_device(self.sample(100)).reshape(-1, 32, 32, 3), int(n / 100), 100, net,
+                                          splits, batch_size)
         return _inception_score_of(self, n, classifier, splits, batch_size)
 
-    def maybe_inception_score(self, classifier, n=50000):
+    def maybe_inception_score(self, classifier=None, n=50000, net=None):
         """The loop hook (:634-637): after `train_iteration`, `self.iteration` counts finished iterations, so the reference's
         `iteration % INCEPTION_FREQUENCY == INCEPTION_FREQUENCY - 1` reads `self.iteration % INCEPTION_FREQUENCY == 0` here.
-        -> (mean, std) when due, else None"""
+        classifier / net: as `inception_score` takes them.  -> (mean, std) when due, else None"""
         if self.iteration > 0 and self.iteration % INCEPTION_FREQUENCY == 0:
-            return self.inception_score(n, classifier)
+            return self.inception_score(n, classifier, net=net)
         return None
 
     @torch.no_grad()

@@ -270,3 +270,10 @@ class InceptionV3:
         f = self.features(images, resize)
         # fp32 logits: the score exponentiates them (16-bit logits at |l| ~ 10 would be +-0.04, a few percent per probability)
         return K.linear_fwd(f, self.fc_w, self.fc_b, out_f32=True).cpu().numpy()
+
+    @torch.no_grad()
+    def logits_device(self, images, resize=299):
+        """-> float32 device tensor [N, 1008]: the kernels of `logits`, launch for launch, without the copy back -- what
+        `InceptionScore.update` takes (common/inception/inception_score.py)"""
+        f = self.features(images, resize)
+        return K.linear_fwd(f, self.fc_w, self.fc_b, out_f32=True)

@@ -1983,6 +1983,34 @@ def moments_update(x, total, gram):
                                          _p(gram, torch.float64, "gram"), _stream()), "moments_update")
 
 
+# ------------------------------------------------------------------ Inception score statistics (common/inception/inception_score.py)
+def inception_score_update(logits, row0, n_total, splits, state, scratch=None):
+    """state float64 [splits, 1001] += the class probabilities (columns 0..999) and sum p log p (column 1000) of the rows of
+    logits float32 [b, >= 1000], global rows row0 .. row0 + b - 1 of n_total, each into the split it belongs to
+    (gank_inception_score_update).  Only the first 1000 columns count; rows may be a view with a row stride >= 1000 and unit
+    column stride (passed as `ld`: [b, 1008] logits, or their first 1000 columns, are not copied).  scratch: float64 [>= b, 2]
+    work space, allocated when None."""
+    if not logits.is_cuda:
+        raise RuntimeError("gank: logits must live on the GPU (no CPU path exists)")
+    if logits.dim() != 2 or logits.dtype != F32 or logits.shape[1] < 1000:
+        raise RuntimeError(f"gank: inception_score_update takes float32 logits [b, >= 1000], got {tuple(logits.shape)} {logits.dtype}")
+    b = logits.shape[0]
+    if b == 0:
+        return
+    ld = logits.stride(0) if b > 1 else max(logits.stride(0), logits.shape[1])
+    if logits.stride(1) != 1 or ld < logits.shape[1]:
+        raise RuntimeError(f"gank: logits rows must be contiguous and not overlap, got strides {logits.stride()} for {tuple(logits.shape)}")
+    if state.dim() != 2 or tuple(state.shape) != (splits, 1001):
+        raise RuntimeError(f"gank: inception_score_update: state {tuple(state.shape)}, expected [{splits}, 1001]")
+    if scratch is None:
+        scratch = torch.empty((b, 2), dtype=torch.float64, device=logits.device)
+    elif scratch.numel() < 2 * b:
+        raise RuntimeError(f"gank: inception_score_update: scratch {tuple(scratch.shape)} is smaller than [{b}, 2]")
+    _lib.check(lib().gank_inception_score_update(C.c_void_p(logits.data_ptr()), b, ld, int(row0), int(n_total), int(splits),
+                                                 _p(state, torch.float64, "state"), _p(scratch, torch.float64, "scratch"), _stream()),
+               "inception_score_update")
+
+
 # ------------------------------------------------------------------ profiler
 def prof_enable(on):
     lib().gank_prof_enable(int(on))

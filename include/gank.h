@@ -925,6 +925,23 @@ int gank_msssim_level_parts(int H, int W, int C, int size);
 int gank_mean_hw_f32(const void* x, float* y, int n, int HW, int C, void* stream);
 int gank_moments_update(const void* x, int dtype, int n, int D, double* sum, double* gram, void* stream);
 
+/* ---- Inception score: the statistics stage (common/inception/inception_score.py: InceptionScore; inception_score.py:49-66 of
+ * the reference, the one filled column of its README's "Quantitative evaluation" table) ----------------------------------
+ * gank_inception_score_update: logits FLOAT32 [n_rows, ld], ld >= 1000, of which the first 1000 columns of a row count
+ *   (:55), are added to the running float64 state [splits, 1001] of the score of n_total rows.  Row r of the call is global
+ *   row row0 + r; a global row belongs to split j when j*n_total/splits <= row < (j+1)*n_total/splits (integer division:
+ *   preds2score's slices, :61, uneven ones too); a call may straddle split boundaries.  Per row, in float64 from the float32
+ *   logits: lse = max + log sum_y exp(l_y - max), p_y = exp(l_y - lse); state[j][y] += p_y for y < 1000 and
+ *   state[j][1000] += sum_y p_y (l_y - lse) -- the log-softmax form of sum p log p, finite where p underflows to 0.
+ *   exp(state[j][1000]/n_j - sum_y m_y log m_y), m_y = state[j][y]/n_j, is split j's score.  Two launches: a row pass writes
+ *   (lse, sum_y p_y (l_y - lse)) per row into scratch [n_rows, 2] (float64, overwritten by every call), a column pass owns
+ *   one state element per thread and adds the call's rows onto the stored value one by one in ascending row order.  No
+ *   atomics; every element receives its rows in global row order from its sole owner, so the same rows fed in calls of any
+ *   sizes, and two identical runs, leave bit-identical state.  The caller zeroes state before the first call.
+ *   Refused: null pointers, n_rows <= 0, ld < 1000, splits < 1, splits > n_total, row0 < 0, row0 + n_rows > n_total. */
+int gank_inception_score_update(const float* logits, int n_rows, int ld, long long row0, long long n_total, int splits, double* state,
+                                double* scratch, void* stream);
+
 /* ---- Pix2Pix input pipeline (Pix2Pix/train.py of the reference) --------------------------------------------------------
  * gank_pix2pix_load_examples: load_examples (train.py:355-431) for a batch, one launch.  raw: uint8 [N,H,Wraw,3] on the
  *   device, 4-byte aligned.  mode 0: pair, A | B of Wraw/2 columns (:395-396); 1: multiple_A, three panels of Wraw/3, A = the
