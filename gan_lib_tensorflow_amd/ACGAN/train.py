@@ -208,6 +208,22 @@ class ACGANTrainer(trainer.GraphTrainer):
         return calculate_fid(sample_moments(draw, n, net), real, net)
 
     @torch.no_grad()
+    def kid(self, real, n=50000, net=None, subsets=100, subset_size=1000, seed=0):
+        """Kernel Inception Distance (common/kid.py: the unbiased polynomial-kernel MMD^2 of the pool_3 features) between n
+        samples and `real`: a FeatureBank, features [N, 2048] or images [N,H,W,3] -> (mean, std) over `subsets` subsets of
+        `subset_size` rows a side.  The samples are those of `fid`, drawn and quantised the same way; samples and features never
+        leave the device.  net: an `InceptionV3` (the frozen graph's weights are a download)."""
+        from ..common.kid import calculate_kid, sample_features
+        from ..common.msssim import quantize_on_device
+        set_default_store(self.store)
+
+        def draw():
+            z = K.rng_normal((self.batch, self.z_dim), self.rng_state)
+            labels = K.rng_labels(self.batch, 10, self.rng_state)
+            return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3)
+        return calculate_kid(sample_features(draw, n, net), real, net, subsets=subsets, subset_size=subset_size, seed=seed)
+
+    @torch.no_grad()
     def inception_score(self, n=50000, net=None, splits=10):
         """get_inception_score(n) of the training script (train.py:159-171, every evaluation_interval steps, :208-211): n / 100
         generator passes of 100 samples on fresh normal noise and fresh uniform labels, quantised as

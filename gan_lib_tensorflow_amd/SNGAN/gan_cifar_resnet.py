@@ -1006,6 +1006,17 @@ class SNGANTrainer:
         from ..common.msssim import quantize_on_device
         return calculate_fid(sample_moments(lambda: quantize_on_device(self.sample(100)).reshape(-1, 32, 32, 3), n, net), real, net)
 
+    @torch.no_grad()
+    def kid(self, real, n=50000, net=None, subsets=100, subset_size=1000, seed=0):
+        """Kernel Inception Distance (common/kid.py: the unbiased polynomial-kernel MMD^2 of the pool_3 features) between n
+        samples and `real`: a FeatureBank, features [N, 2048] or images [N,H,W,3] -> (mean, std) over `subsets` subsets of
+        `subset_size` rows a side.  The samples are those of `fid`, drawn and quantised the same way; samples and features never
+        leave the device.  net: an `InceptionV3` (the frozen graph's weights are a download)."""
+        from ..common.kid import calculate_kid, sample_features
+        from ..common.msssim import quantize_on_device
+        bank = sample_features(lambda: quantize_on_device(self.sample(100)).reshape(-1, 32, 32, 3), n, net)
+        return calculate_kid(bank, real, net, subsets=subsets, subset_size=subset_size, seed=seed)
+
 
 def _inception_score_of(trainer, n, classifier, splits, batch_size):
     """(:543-555)  n / 100 calls of `samples_100` -- a Generator(100, ...) pass on fresh uniform labels and fresh noise, batch

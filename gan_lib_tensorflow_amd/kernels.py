@@ -2011,6 +2011,56 @@ def inception_score_update(logits, row0, n_total, splits, state, scratch=None):
                "inception_score_update")
 
 
+# ------------------------------------------------------------------ Kernel Inception Distance statistics (common/kid.py)
+def kid_num_tiles(m):
+    """the tile partials gank_kid_block_sums writes per subset of m rows: with T = ceil(m / 64), T (T + 1) / 2 for XX, as many
+    for YY and T * T for XY, in that order (include/gank.h)"""
+    t = (int(m) + 63) // 64
+    return t * (t + 1) + t * t
+
+
+def kid_block_sums(x, y, ix, iy, gamma, coef0, degree=3, partial=None, out=None):
+    """x float32 [nx, D], y float32 [ny, D], row tables ix, iy int32 [subsets, m] -> float64 [subsets, 3] on the device: per subset
+    (sum over i != j of k(x_i, x_j), the same of y, sum over all i, j of k(x_i, y_j)) with k(a, b) = (gamma <a, b> + coef0)^degree
+    (gank_kid_block_sums, gank_kid_finish).  The tables may be NumPy arrays or tensors on either side; their entries are
+    checked against nx / ny here, because the kernel cannot refuse them.  partial float64 [>= subsets * kid_num_tiles(m)] and
+    out float64 [>= subsets * 3]: work space and result buffer, allocated when None."""
+    for name, f in (("x", x), ("y", y)):
+        if not f.is_cuda:
+            raise RuntimeError(f"gank: {name} must live on the GPU (no CPU path exists)")
+        if f.dim() != 2 or f.dtype != F32:
+            raise RuntimeError(f"gank: kid_block_sums takes float32 features [n, D], got {name} {tuple(f.shape)} {f.dtype}")
+    if x.shape[1] != y.shape[1]:
+        raise RuntimeError(f"gank: kid_block_sums: x {tuple(x.shape)} and y {tuple(y.shape)} differ in the feature width")
+    tables = []
+    for name, t, n in (("ix", ix, x.shape[0]), ("iy", iy, y.shape[0])):
+        t = torch.as_tensor(t)
+        if t.dim() != 2 or t.dtype != I32:
+            raise RuntimeError(f"gank: kid_block_sums takes int32 row tables [subsets, m], got {name} {tuple(t.shape)} {t.dtype}")
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
+            raise RuntimeError(f"gank: kid_block_sums: {name} names rows {int(t.min())}..{int(t.max())} of a bank of {n}")
+        tables.append(t.to(x.device).contiguous())
+    ix, iy = tables
+    if ix.shape != iy.shape:
+        raise RuntimeError(f"gank: kid_block_sums: ix {tuple(ix.shape)} and iy {tuple(iy.shape)} differ")
+    subsets, m = ix.shape
+    need = subsets * kid_num_tiles(m)
+    if partial is None:
+        partial = torch.empty(need, dtype=torch.float64, device=x.device)
+    elif partial.numel() < need:
+        raise RuntimeError(f"gank: kid_block_sums: partial {tuple(partial.shape)} holds fewer than {need} tile sums")
+    if out is None:
+        out = torch.empty((subsets, 3), dtype=torch.float64, device=x.device)
+    elif out.numel() < subsets * 3:
+        raise RuntimeError(f"gank: kid_block_sums: out {tuple(out.shape)} is smaller than [{subsets}, 3]")
+    _lib.check(lib().gank_kid_block_sums(_p(x, F32, "x"), x.shape[0], _p(y, F32, "y"), y.shape[0], x.shape[1], _p(ix, I32, "ix"),
+                                         _p(iy, I32, "iy"), subsets, m, float(gamma), float(coef0), int(degree),
+                                         _p(partial, torch.float64, "partial"), _stream()), "kid_block_sums")
+    _lib.check(lib().gank_kid_finish(_p(partial, torch.float64, "partial"), subsets, m, _p(out, torch.float64, "out"), _stream()),
+               "kid_finish")
+    return out.view(-1)[:subsets * 3].view(subsets, 3)
+
+
 # ------------------------------------------------------------------ profiler
 def prof_enable(on):
     lib().gank_prof_enable(int(on))

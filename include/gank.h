@@ -942,6 +942,27 @@ int gank_moments_update(const void* x, int dtype, int n, int D, double* sum, dou
 int gank_inception_score_update(const float* logits, int n_rows, int ld, long long row0, long long n_total, int splits, double* state,
                                 double* scratch, void* stream);
 
+/* ---- Kernel Inception Distance: the statistics stage (common/kid.py: polynomial_mmd2; the unbiased MMD^2 of Binkowski et
+ * al., "Demystifying MMD GANs", on the pool_3 features FID uses) -----------------------------------------------------------
+ * gank_kid_block_sums: x FLOAT32 [nx,D] and y FLOAT32 [ny,D] are feature banks, ix and iy int32 [subsets,m] row tables:
+ *   subset s is the rows x[ix[s][.]] and y[iy[s][.]].  With k(a, b) = (gamma <a, b> + coef0)^degree in float64 (the dot
+ *   products on v_mfma_f64_16x16x4_f64, contraction over the feature axis; t^degree by repeated multiplication) the m x m
+ *   kernel matrices of the blocks XX, YY and XY of every subset are summed per 64 x 64 tile, T = ceil(m / 64) tiles a side:
+ *   XX and YY own only the tri = T (T + 1) / 2 tiles with bi <= bj, enumerated row by row; an off-diagonal tile's sum is
+ *   stored DOUBLED (here, not in gank_kid_finish) and a diagonal tile leaves out its elements i == j: the unbiased estimator.
+ *   XY owns all T * T tiles, row-major.  partial: float64 [subsets][2 tri + T * T]: per subset the tiles of XX, then of YY,
+ *   then of XY (the blocks start at 0, tri and 2 tri); every entry is written by one plain store of its sole owner.  No
+ *   atomics and no split of the contraction: bit-identical from call to call.
+ *   Refused: null pointers; D % 16 != 0 or D outside 16..4096 (the rule of gank_moments_update); m < 2, m > nx, m > ny,
+ *   m > 65536; subsets outside 1..65535; degree outside 1..3; x / y not 16-byte aligned.  The tables are device memory the
+ *   host cannot see: a row outside [0, nx) / [0, ny) is the caller's error (kernels.kid_block_sums checks before upload).
+ * gank_kid_finish: out float64 [subsets,3] = (sum of XX over i != j, sum of YY over i != j, sum of XY) per subset: one wave
+ *   per (subset, block) adds that block's tile partials in index order (lane l the tiles l, l + 64, ..; then a fixed
+ *   cross-lane tree).  It applies no weights. */
+int gank_kid_block_sums(const float* x, int nx, const float* y, int ny, int D, const int* ix, const int* iy, int subsets, int m,
+                        double gamma, double coef0, int degree, double* partial, void* stream);
+int gank_kid_finish(const double* partial, int subsets, int m, double* out, void* stream);
+
 /* ---- Pix2Pix input pipeline (Pix2Pix/train.py of the reference) --------------------------------------------------------
  * gank_pix2pix_load_examples: load_examples (train.py:355-431) for a batch, one launch.  raw: uint8 [N,H,Wraw,3] on the
  *   device, 4-byte aligned.  mode 0: pair, A | B of Wraw/2 columns (:395-396); 1: multiple_A, three panels of Wraw/3, A = the
