@@ -224,6 +224,25 @@ class ACGANTrainer(trainer.GraphTrainer):
         return calculate_kid(sample_features(draw, n, net), real, net, subsets=subsets, subset_size=subset_size, seed=seed)
 
     @torch.no_grad()
+    def precision_recall(self, real, n=10000, net=None, k=3):
+        """Precision, recall, density and coverage (common/precision_recall.py: k-NN manifolds of the pool_3 features) of n
+        samples against `real`: a FeatureBank, features [N, 2048] or images [N,H,W,3] -> dict(precision, recall, density,
+        coverage).  The samples are those of `kid`, drawn and quantised the same way; samples and features never leave the
+        device.  The default n is 10 000, not 50 000: in float64 a distance matrix costs 2 n^2 D FLOP per pass and there are
+        four passes, 0.41 TFLOP a pass at 10 000 and 10 TFLOP at 50 000 (25 times the time and, for the n samples, five times the
+        Inception forwards).  net: an `InceptionV3` (the frozen graph's weights are a download)."""
+        from ..common.kid import sample_features
+        from ..common.msssim import quantize_on_device
+        from ..common.precision_recall import calculate_prdc
+        set_default_store(self.store)
+
+        def draw():
+            z = K.rng_normal((self.batch, self.z_dim), self.rng_state)
+            labels = K.rng_labels(self.batch, 10, self.rng_state)
+            return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3)
+        return calculate_prdc(real, sample_features(draw, n, net), net, k)
+
+    @torch.no_grad()
     def inception_score(self, n=50000, net=None, splits=10):
         """get_inception_score(n) of the training script (train.py:159-171, every evaluation_interval steps, :208-211): n / 100
         generator passes of 100 samples on fresh normal noise and fresh uniform labels, quantised as

@@ -1017,6 +1017,20 @@ class SNGANTrainer:
         bank = sample_features(lambda: quantize_on_device(self.sample(100)).reshape(-1, 32, 32, 3), n, net)
         return calculate_kid(bank, real, net, subsets=subsets, subset_size=subset_size, seed=seed)
 
+    @torch.no_grad()
+    def precision_recall(self, real, n=10000, net=None, k=3):
+        """Precision, recall, density and coverage (common/precision_recall.py: k-NN manifolds of the pool_3 features) of n
+        samples against `real`: a FeatureBank, features [N, 2048] or images [N,H,W,3] -> dict(precision, recall, density,
+        coverage).  The samples are those of `kid`, drawn and quantised the same way; samples and features never leave the
+        device.  The default n is 10 000, not 50 000: in float64 a distance matrix costs 2 n^2 D FLOP per pass and there are
+        four passes, 0.41 TFLOP a pass at 10 000 and 10 TFLOP at 50 000 (25 times the time and, for the n samples, five times the
+        Inception forwards).  net: an `InceptionV3` (the frozen graph's weights are a download)."""
+        from ..common.kid import sample_features
+        from ..common.msssim import quantize_on_device
+        from ..common.precision_recall import calculate_prdc
+        bank = sample_features(lambda: quantize_on_device(self.sample(100)).reshape(-1, 32, 32, 3), n, net)
+        return calculate_prdc(real, bank, net, k)
+
 
 def _inception_score_of(trainer, n, classifier, splits, batch_size):
     """(:543-555)  n / 100 calls of `samples_100` -- a Generator(100, ...) pass on fresh uniform labels and fresh noise, batch

@@ -245,6 +245,10 @@ PROTOTYPES = {
     "gank_inception_score_update": [P, I, I, C.c_longlong, C.c_longlong, I, P, P, P],
     "gank_kid_block_sums": [P, I, P, I, I, P, P, I, I, C.c_double, C.c_double, I, P, P],
     "gank_kid_finish": [P, I, I, P, P],
+    "gank_prd_knn_partial": [P, I, I, I, I, P, P],
+    "gank_prd_knn_finish": [P, I, I, I, P, P],
+    "gank_prd_counts_partial": [P, I, P, I, I, P, I, P, P, P],
+    "gank_prd_counts_finish": [P, P, I, I, P, P, P],
     "gank_pix2pix_load_examples": [P, I, I, I, I, I, I, I, I, P, P, P, I, P],
     "gank_rgb_to_lab": [P, P, L, P],
     "gank_lab_to_rgb": [P, P, L, P],

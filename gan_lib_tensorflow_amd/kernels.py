@@ -2061,6 +2061,97 @@ def kid_block_sums(x, y, ix, iy, gamma, coef0, degree=3, partial=None, out=None)
     return out.view(-1)[:subsets * 3].view(subsets, 3)
 
 
+# ------------------------------------------------------------------ precision / recall, density / coverage (common/precision_recall.py)
+def prd_default_segments(n, rows=None):
+    """The column segments `prd_knn_radii` / `prd_manifold_counts` cut a bank of n rows into when segments=None (rows: the
+    query rows, n when None).  A workgroup owns 64 rows x one segment and a segment is whole 64-column tiles, so the grid
+    is ceil(rows / 64) x segments workgroups of about equal length: enough segments for 16 workgroups per compute unit
+    (256 of them; 2 are resident on a unit at once, the rest queue), so that the busiest unit's share is within about one
+    workgroup in 16 of the mean, and never more than there are column tiles.  Measured at 10 000 x 10 000 x 2048 (157 strips;
+    scratch/bench_prd.py): 3 segments 8.9 ms a radii pass, 6 8.8 ms, 14 8.5 ms, 27 (this rule) 8.2 ms."""
+    strips = (int(n if rows is None else rows) + 63) // 64
+    tiles = (int(n) + 63) // 64
+    return max(1, min(tiles, -(-16 * 256 // strips)))
+
+
+def prd_counts_partial_len(nq, segments):
+    """float64 elements of the work space of `prd_manifold_counts`: nq * segments minima, then as many int32 counts"""
+    m = int(nq) * int(segments)
+    return m + (m + 1) // 2
+
+
+def _prd_features(what, **sides):
+    for name, f in sides.items():
+        if not f.is_cuda:
+            raise RuntimeError(f"gank: {name} must live on the GPU (no CPU path exists)")
+        if f.dim() != 2 or f.dtype != F32:
+            raise RuntimeError(f"gank: {what} takes float32 features [n, D], got {name} {tuple(f.shape)} {f.dtype}")
+
+
+def prd_knn_radii(x, k, segments=None, part=None, out=None):
+    """x float32 [n, D] -> float64 [n] on the device: per row the SQUARED distance to its k-th nearest other row of x (1 <= k
+    <= 8, n >= k + 1; the row itself is left out by index, so a duplicate is a neighbour at distance 0), in float64
+    (gank_prd_knn_partial, gank_prd_knn_finish).  segments: the cut of the columns (prd_default_segments(n) when None); the
+    result does not depend on it.  part float64 [>= n * segments * k] and out float64 [>= n]: work space and result buffer,
+    allocated when None."""
+    _prd_features("prd_knn_radii", x=x)
+    n, k = x.shape[0], int(k)
+    segments = prd_default_segments(n) if segments is None else int(segments)
+    need = n * max(segments, 0) * max(k, 0)
+    if part is None:
+        part = torch.empty(max(need, 1), dtype=torch.float64, device=x.device)
+    elif part.numel() < need:
+        raise RuntimeError(f"gank: prd_knn_radii: part {tuple(part.shape)} holds fewer than {need} values")
+    if out is None:
+        out = torch.empty(max(n, 1), dtype=torch.float64, device=x.device)
+    elif out.numel() < n:
+        raise RuntimeError(f"gank: prd_knn_radii: out {tuple(out.shape)} is smaller than [{n}]")
+    _lib.check(lib().gank_prd_knn_partial(_p(x, F32, "x"), n, x.shape[1], k, segments, _p(part, torch.float64, "part"), _stream()),
+               "prd_knn_radii")
+    _lib.check(lib().gank_prd_knn_finish(_p(part, torch.float64, "part"), n, k, segments, _p(out, torch.float64, "out"), _stream()),
+               "prd_knn_finish")
+    return out.view(-1)[:n]
+
+
+def prd_manifold_counts(q, r, radii2, segments=None, partial=None, counts=None, nearest=None):
+    """Queries q float32 [nq, D], a bank r float32 [nr, D] and its squared radii float64 [nr] (`prd_knn_radii`) -> (int32 [nq],
+    float64 [nq]) on the device: per query row the number of bank rows j with d2(q_i, r_j) <= radii2[j] (inclusive) and
+    min_j d2(q_i, r_j), in float64 (gank_prd_counts_partial, gank_prd_counts_finish).  Nothing is left out when q is r.
+    segments: the cut of the bank (prd_default_segments(nr, nq) when None); the result does not depend on it.  partial float64
+    [>= prd_counts_partial_len(nq, segments)], counts int32 [>= nq], nearest float64 [>= nq]: work space and result buffers,
+    allocated when None."""
+    _prd_features("prd_manifold_counts", q=q, r=r)
+    if q.shape[1] != r.shape[1]:
+        raise RuntimeError(f"gank: prd_manifold_counts: q {tuple(q.shape)} and r {tuple(r.shape)} differ in the feature width")
+    nq, nr = q.shape[0], r.shape[0]
+    if radii2.dtype != torch.float64 or tuple(radii2.shape) != (nr,):
+        raise RuntimeError(f"gank: prd_manifold_counts takes radii2 float64 [{nr}], got {tuple(radii2.shape)} {radii2.dtype}")
+    segments = prd_default_segments(nr, nq) if segments is None else int(segments)
+    m = nq * max(segments, 0)
+    need = prd_counts_partial_len(nq, max(segments, 0))
+    if partial is None:
+        partial = torch.empty(max(need, 2), dtype=torch.float64, device=q.device)
+    elif partial.numel() < need:
+        raise RuntimeError(f"gank: prd_manifold_counts: partial {tuple(partial.shape)} holds fewer than {need} values")
+    if counts is None:
+        counts = torch.empty(max(nq, 1), dtype=I32, device=q.device)
+    elif counts.numel() < nq:
+        raise RuntimeError(f"gank: prd_manifold_counts: counts {tuple(counts.shape)} is smaller than [{nq}]")
+    if nearest is None:
+        nearest = torch.empty(max(nq, 1), dtype=torch.float64, device=q.device)
+    elif nearest.numel() < nq:
+        raise RuntimeError(f"gank: prd_manifold_counts: nearest {tuple(nearest.shape)} is smaller than [{nq}]")
+    _p(partial, torch.float64, "partial")
+    part_min = partial.view(-1)[:m]
+    part_count = partial.view(-1)[m:].view(I32)      # the counts live behind the minima, 8-byte aligned
+    _lib.check(lib().gank_prd_counts_partial(_p(q, F32, "q"), nq, _p(r, F32, "r"), nr, q.shape[1], _p(radii2, torch.float64, "radii2"),
+                                             segments, _p(part_count, I32, "partial"), _p(part_min, torch.float64, "partial"), _stream()),
+               "prd_manifold_counts")
+    _lib.check(lib().gank_prd_counts_finish(_p(part_count, I32, "partial"), _p(part_min, torch.float64, "partial"), nq, segments,
+                                            _p(counts, I32, "counts"), _p(nearest, torch.float64, "nearest"), _stream()), "prd_counts_finish")
+    return counts.view(-1)[:nq], nearest.view(-1)[:nq]
+
+
 # ------------------------------------------------------------------ profiler
 def prof_enable(on):
     lib().gank_prof_enable(int(on))

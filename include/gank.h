@@ -963,6 +963,31 @@ int gank_kid_block_sums(const float* x, int nx, const float* y, int ny, int D, c
                         double gamma, double coef0, int degree, double* partial, void* stream);
 int gank_kid_finish(const double* partial, int subsets, int m, double* out, void* stream);
 
+/* ---- Precision / recall and density / coverage: the statistics stage (common/precision_recall.py; Kynkaanniemi et al.,
+ * "Improved Precision and Recall Metric for Assessing Generative Models"; Naeem et al., "Reliable Fidelity and Diversity
+ * Metrics for Generative Models"; on the pool_3 features FID and KID use) ------------------------------------------------
+ * Squared distances d2_ij = (|a_i|^2 + |b_j|^2) - 2 <a_i, b_j> in float64 on FLOAT32 features (the dot products on
+ * v_mfma_f64_16x16x4_f64, contraction over the feature axis; the norms by a fixed-order float64 sum), clamped at 0.  A
+ * workgroup owns a strip of 64 rows and one of `segments` contiguous ranges of the T = ceil(columns / 64) column tiles,
+ * segment s = tiles [T s / segments, T (s + 1) / segments); the full matrix is computed.  No atomics and no split of the
+ * contraction: bit-identical from call to call and for every segment count.
+ * gank_prd_knn_partial: x [n,D]; part float64 [n][segments][k]: per row and segment the k smallest d2 to the OTHER rows
+ *   (j != i by index: a duplicated row is a neighbour at distance 0) among the segment's columns, ascending, padded with
+ *   +inf; every entry is written by one plain store.
+ * gank_prd_knn_finish: radii2 float64 [n] = the k-th smallest of a row's segments * k values: the squared k-NN radius.
+ * gank_prd_counts_partial: q [nq,D] queries, r [nr,D] the bank, radii2 float64 [nr]; per query row and segment
+ *   part_count int32 [nq][segments] = the number of the segment's columns j with d2_ij <= radii2[j] (inclusive) and
+ *   part_min float64 [nq][segments] = their smallest d2_ij.  No self-exclusion.
+ * gank_prd_counts_finish: count int32 [nq] = the sum, nearest2 float64 [nq] = the minimum over the segments.
+ *   Refused: null pointers; D % 16 != 0 or D outside 16..4096 (the rule of gank_kid_block_sums); k outside 1..8; n < k + 1;
+ *   nq < 1, nr < 1; more than 2^24 rows a side; segments < 1, > 65535 or more than the column tiles; features not 16-byte
+ *   aligned. */
+int gank_prd_knn_partial(const float* x, int n, int D, int k, int segments, double* part, void* stream);
+int gank_prd_knn_finish(const double* part, int n, int k, int segments, double* radii2, void* stream);
+int gank_prd_counts_partial(const float* q, int nq, const float* r, int nr, int D, const double* radii2, int segments, int* part_count,
+                            double* part_min, void* stream);
+int gank_prd_counts_finish(const int* part_count, const double* part_min, int nq, int segments, int* count, double* nearest2, void* stream);
+
 /* ---- Pix2Pix input pipeline (Pix2Pix/train.py of the reference) --------------------------------------------------------
  * gank_pix2pix_load_examples: load_examples (train.py:355-431) for a batch, one launch.  raw: uint8 [N,H,Wraw,3] on the
  *   device, 4-byte aligned.  mode 0: pair, A | B of Wraw/2 columns (:395-396); 1: multiple_A, three panels of Wraw/3, A = the
