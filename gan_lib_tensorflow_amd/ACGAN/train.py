@@ -243,6 +243,22 @@ class ACGANTrainer(trainer.GraphTrainer):
         return calculate_prdc(real, sample_features(draw, n, net), net, k)
 
     @torch.no_grad()
+    def swd(self, real, n=8192, seed=0, **kw):
+        """Sliced Wasserstein distance on Laplacian-pyramid patches (common/swd.py; Karras et al. 2018, section 5: no network,
+        no downloaded weights) between n samples and the first n images of `real` [N >= n, 32, 32, 3] (uint8 or float32, NumPy
+        or device tensor) -> (float64 [levels], their mean), x 1000.  The samples are those of `fid`, drawn and quantised the
+        same way; they never leave the device.  **kw: nhood_size, nhoods_per_image, dir_repeats, dirs_per_repeat."""
+        from ..common.msssim import quantize_on_device
+        from ..common.swd import sample_swd
+        set_default_store(self.store)
+
+        def draw():
+            z = K.rng_normal((self.batch, self.z_dim), self.rng_state)
+            labels = K.rng_labels(self.batch, 10, self.rng_state)
+            return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3)
+        return sample_swd(draw, real, n, seed, **kw)
+
+    @torch.no_grad()
     def inception_score(self, n=50000, net=None, splits=10):
         """get_inception_score(n) of the training script (train.py:159-171, every evaluation_interval steps, :208-211): n / 100
         generator passes of 100 samples on fresh normal noise and fresh uniform labels, quantised as

@@ -144,3 +144,17 @@ class PGGANTrainer(GraphTrainer):
         size = self.args.image_size
         return sample_inception_score(lambda: quantize_on_device(self.sample(100, alpha=alpha)).reshape(-1, size, size, 3), int(n / 100), 100,
                                       net, splits)
+
+    @torch.no_grad()
+    def swd(self, real, n=8192, alpha=None, seed=0, **kw):
+        """Sliced Wasserstein distance on Laplacian-pyramid patches, the metric of the progressive-GAN paper's tables (Karras et
+        al. 2018, section 5; common/swd.py: no network, no downloaded weights), between n samples and the first n images of
+        `real` [N >= n, image_size, image_size, 3] (uint8 or float32, NumPy or device tensor; already at the stage's size) ->
+        (float64 [levels], their mean), x 1000: one value per pyramid level from image_size down to 16.  The samples are those
+        of `inception_score`: generator passes of 100 on fresh noise at `alpha` (default: the current fade-in weight), quantised
+        the same way; they never leave the device.  At image_size 4 it raises: a 7 x 7 patch does not fit.
+        **kw: nhood_size, nhoods_per_image, dir_repeats, dirs_per_repeat."""
+        from ..common.msssim import quantize_on_device
+        from ..common.swd import sample_swd
+        size = self.args.image_size
+        return sample_swd(lambda: quantize_on_device(self.sample(100, alpha=alpha)).reshape(-1, size, size, 3), real, n, seed, **kw)

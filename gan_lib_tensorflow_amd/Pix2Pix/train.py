@@ -383,3 +383,12 @@ def msssim_score(outputs, targets, weights=None, per_image=False):
     after the shift to [0, 2].  One float with the reference's batch semantics, or float64 [N] with per_image=True."""
     from ..common.msssim import MultiScaleSSIM
     return MultiScaleSSIM(outputs.float() + 1.0, targets.float() + 1.0, max_val=2.0, weights=weights, per_image=per_image)
+
+
+@torch.no_grad()
+def swd_score(outputs, targets, **kw):
+    """Sliced Wasserstein distance on Laplacian-pyramid patches (common/swd.py) of generator outputs against their targets, both
+    [N,H,W,C] in [-1, 1] as the model produces / is fed them (any 16-bit or fp32 dtype), scored as float64 ->
+    (float64 [levels], their mean), x 1000.  **kw: nhood_size, nhoods_per_image, dir_repeats, dirs_per_repeat, seed."""
+    from ..common.swd import calculate_swd
+    return calculate_swd(outputs.float(), targets.float(), **kw)

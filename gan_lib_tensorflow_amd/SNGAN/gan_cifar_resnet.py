@@ -1031,6 +1031,16 @@ class SNGANTrainer:
         bank = sample_features(lambda: quantize_on_device(self.sample(100)).reshape(-1, 32, 32, 3), n, net)
         return calculate_prdc(real, bank, net, k)
 
+    @torch.no_grad()
+    def swd(self, real, n=8192, seed=0, **kw):
+        """Sliced Wasserstein distance on Laplacian-pyramid patches (common/swd.py; Karras et al. 2018, section 5: no network,
+        no downloaded weights) between n samples and the first n images of `real` [N >= n, 32, 32, 3] (uint8 or float32, NumPy
+        or device tensor) -> (float64 [levels], their mean), x 1000.  The samples are those of `fid`, drawn and quantised the
+        same way; they never leave the device.  **kw: nhood_size, nhoods_per_image, dir_repeats, dirs_per_repeat."""
+        from ..common.msssim import quantize_on_device
+        from ..common.swd import sample_swd
+        return sample_swd(lambda: quantize_on_device(self.sample(100)).reshape(-1, 32, 32, 3), real, n, seed, **kw)
+
 
 def _inception_score_of(trainer, n, classifier, splits, batch_size):
     """(:543-555)  n / 100 calls of `samples_100` -- a Generator(100, ...) pass on fresh uniform labels and fresh noise, batch

@@ -249,12 +249,22 @@ PROTOTYPES = {
     "gank_prd_knn_finish": [P, I, I, I, P, P],
     "gank_prd_counts_partial": [P, I, P, I, I, P, I, P, P, P],
     "gank_prd_counts_finish": [P, P, I, I, P, P, P],
+    "gank_swd_pyr_down": [P, I, I, I, I, P, P],
+    "gank_swd_laplacian": [P, P, I, I, I, I, P],
+    "gank_swd_patch_stats_parts": [I],
+    "gank_swd_patch_stats": [P, I, I, I, I, P, P, I, I, I, P, P, P, P],
+    "gank_swd_project": [P, I, I, I, I, P, P, I, I, I, P, P, I, P, P],
+    "gank_swd_sort_max_rows": [],
+    "gank_swd_sort_ws_elems": [I, I],
+    "gank_swd_sort_rows": [P, P, I, I, P, P],
+    "gank_swd_sorted_l1_parts": [I],
+    "gank_swd_sorted_l1": [P, P, I, I, P, P],
     "gank_pix2pix_load_examples": [P, I, I, I, I, I, I, I, I, P, P, P, I, P],
     "gank_rgb_to_lab": [P, P, L, P],
     "gank_lab_to_rgb": [P, P, L, P],
     "gank_pix2pix_convert_u8": [P, P, I, L, I, I, I, I, P, P],
 }
-_RET = {"gank_last_error": C.c_char_p, "gank_sn_ws_floats": C.c_long, "gank_cbn_bwd_ws_floats": C.c_long, "gank_label_conv3x3_bwd_ws_floats": C.c_long, "gank_conv2d_wgrad_ws_elems": C.c_long, "gank_convpool3x3_wgrad_ws_elems": C.c_long, "gank_upconv3x3_wgrad_ws_elems": C.c_long, "gank_conv2d_wgrad_batched_ws_elems": C.c_long, "gank_conv2d_wgrad_slab_elems": C.c_long, "gank_prof_calibrate": C.c_double, "gank_prof_bytes": C.c_double}
+_RET = {"gank_last_error": C.c_char_p, "gank_sn_ws_floats": C.c_long, "gank_cbn_bwd_ws_floats": C.c_long, "gank_label_conv3x3_bwd_ws_floats": C.c_long, "gank_conv2d_wgrad_ws_elems": C.c_long, "gank_convpool3x3_wgrad_ws_elems": C.c_long, "gank_upconv3x3_wgrad_ws_elems": C.c_long, "gank_conv2d_wgrad_batched_ws_elems": C.c_long, "gank_conv2d_wgrad_slab_elems": C.c_long, "gank_swd_sort_ws_elems": C.c_long, "gank_prof_calibrate": C.c_double, "gank_prof_bytes": C.c_double}
 
 _lib = None
 

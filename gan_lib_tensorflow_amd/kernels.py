@@ -2152,6 +2152,177 @@ def prd_manifold_counts(q, r, radii2, segments=None, partial=None, counts=None, 
     return counts.view(-1)[:nq], nearest.view(-1)[:nq]
 
 
+# ------------------------------------------------------------------ sliced Wasserstein distance (common/swd.py)
+F64 = torch.float64
+
+
+def _swd_level(what, x, name="level"):
+    if not x.is_cuda:
+        raise RuntimeError(f"gank: {name} must live on the GPU (no CPU path exists)")
+    if x.dim() != 4 or x.dtype != F64:
+        raise RuntimeError(f"gank: {what} takes float64 images [N,H,W,C], got {name} {tuple(x.shape)} {x.dtype}")
+    return tuple(x.shape)
+
+
+def _swd_out(what, name, buf, need, dtype, device):
+    """a result / work-space buffer of at least `need` elements: allocated when None, refused when too small"""
+    if buf is None:
+        return torch.empty(max(need, 1), dtype=dtype, device=device)
+    if buf.numel() < need:
+        raise RuntimeError(f"gank: {what}: {name} {tuple(buf.shape)} holds fewer than {need} values")
+    return buf
+
+
+def swd_pyr_down(x, out=None):
+    """x float64 [N,H,W,C] (even sides >= 4) -> float64 [N,H/2,W/2,C]: the 5 x 5 binomial window with mirror boundaries, even
+    rows and columns kept (gank_swd_pyr_down).  out float64 [>= N * H/2 * W/2 * C]: the result buffer, allocated when None."""
+    n, h, w, c = _swd_level("swd_pyr_down", x, "x")
+    need = n * (h // 2) * (w // 2) * c
+    out = _swd_out("swd_pyr_down", "out", out, need, F64, x.device)
+    _lib.check(lib().gank_swd_pyr_down(_p(x, F64, "x"), n, h, w, c, _p(out, F64, "out"), _stream()), "swd_pyr_down")
+    return out.view(-1)[:need].view(n, h // 2, w // 2, c)
+
+
+def swd_laplacian(fine, coarse):
+    """fine float64 [N,H,W,C] -= pyr_up(coarse float64 [N,H/2,W/2,C]) in place (gank_swd_laplacian); returns fine"""
+    n, h, w, c = _swd_level("swd_laplacian", fine, "fine")
+    _swd_level("swd_laplacian", coarse, "coarse")
+    if h % 2 or w % 2 or tuple(coarse.shape) != (n, h // 2, w // 2, c):
+        raise RuntimeError(f"gank: swd_laplacian: coarse {tuple(coarse.shape)} is not the half-size level of fine {tuple(fine.shape)}")
+    _lib.check(lib().gank_swd_laplacian(_p(fine, F64, "fine"), _p(coarse, F64, "coarse"), n, h, w, c, _stream()), "swd_laplacian")
+    return fine
+
+
+def _swd_centres(what, level, cx, cy, nhood_size, nhoods_per_image):
+    """the centre tables int32 [M] checked on the host and uploaded -> (cx, cy, M)"""
+    n, h, w, _ = level.shape
+    nhood_size, nhoods_per_image = int(nhood_size), int(nhoods_per_image)
+    if nhood_size < 1 or nhood_size % 2 == 0 or nhood_size > min(h, w):
+        raise RuntimeError(f"gank: {what}: nhood_size = {nhood_size} (odd, at most the level's sides {h} x {w})")
+    half, tables = nhood_size // 2, []
+    for name, t, side in (("cx", cx, w), ("cy", cy, h)):
+        t = torch.as_tensor(t if getattr(t, "flags", None) is None or t.flags.writeable else t.copy())
+        if t.dim() != 1 or t.dtype != I32:
+            raise RuntimeError(f"gank: {what} takes int32 centre tables [M], got {name} {tuple(t.shape)} {t.dtype}")
+        if t.numel() and (int(t.min()) < half or int(t.max()) >= side - half):
+            raise RuntimeError(f"gank: {what}: {name} in [{int(t.min())}, {int(t.max())}] is outside [{half}, {side - half})")
+        tables.append(t.to(level.device).contiguous())
+    cx, cy = tables
+    m = cx.numel()
+    if cy.numel() != m or m < 1:
+        raise RuntimeError(f"gank: {what}: cx {tuple(cx.shape)} and cy {tuple(cy.shape)} differ or are empty")
+    if nhoods_per_image < 1 or m > nhoods_per_image * n:
+        raise RuntimeError(f"gank: {what}: {m} patches at {nhoods_per_image} per image need more than the {n} images")
+    return cx, cy, m
+
+
+def swd_patch_stats(level, cx, cy, nhood_size, nhoods_per_image, shift=None, part=None, out=None):
+    """level float64 [N,H,W,C], centre tables cx, cy int32 [M] (NumPy or tensor; patch r lies in image r // nhoods_per_image)
+    -> float64 [C, 2] on the device: per channel sum (x - shift[c]) and sum (x - shift[c])^2 over the elements of all patches
+    (gank_swd_patch_stats).  shift: float64 [C] (NumPy or tensor), zero when None.  Centres outside [h, side - h), h =
+    nhood_size // 2, are refused here, because the kernel cannot refuse them.  part float64 [>= swd_patch_stats_parts(M) * C * 2]
+    and out float64 [>= C * 2]: work space and result buffer, allocated when None."""
+    _, _, _, c = _swd_level("swd_patch_stats", level)
+    n, h, w = level.shape[:3]
+    cx, cy, m = _swd_centres("swd_patch_stats", level, cx, cy, nhood_size, nhoods_per_image)
+    if shift is not None:
+        shift = torch.as_tensor(shift)
+        if shift.dtype != F64 or tuple(shift.shape) != (c,):
+            raise RuntimeError(f"gank: swd_patch_stats takes shift float64 [{c}], got {tuple(shift.shape)} {shift.dtype}")
+        shift = shift.to(level.device).contiguous()
+    part = _swd_out("swd_patch_stats", "part", part, swd_patch_stats_parts(m) * c * 2, F64, level.device)
+    out = _swd_out("swd_patch_stats", "out", out, c * 2, F64, level.device)
+    _lib.check(lib().gank_swd_patch_stats(_p(level, F64, "level"), n, h, w, c, _p(cx, I32, "cx"), _p(cy, I32, "cy"), m, int(nhood_size),
+                                          int(nhoods_per_image), _p(shift, F64, "shift"), _p(part, F64, "part"), _p(out, F64, "out"),
+                                          _stream()), "swd_patch_stats")
+    return out.view(-1)[:c * 2].view(c, 2)
+
+
+def swd_patch_stats_parts(m):
+    """the workgroup partials gank_swd_patch_stats writes for m patches"""
+    return (int(m) + 255) // 256
+
+
+def swd_project(level, cx, cy, nhood_size, nhoods_per_image, mean, std, dirs, out=None):
+    """level float64 [N,H,W,C], centre tables int32 [M], mean and std float64 [C] (NumPy or tensor), dirs float64 [K, ndirs] on
+    the device with K = C * nhood_size^2 in (channel, y, x) order -> keys float64 [ndirs, M]: every patch, normalised per channel,
+    projected on every direction (gank_swd_project).  Centres are checked as in `swd_patch_stats`; a std that is not > 0 is
+    refused.  out float64 [>= ndirs * M]: the result buffer, allocated when None."""
+    _, _, _, c = _swd_level("swd_project", level)
+    n, h, w = level.shape[:3]
+    cx, cy, m = _swd_centres("swd_project", level, cx, cy, nhood_size, nhoods_per_image)
+    ms = []
+    for name, t in (("mean", mean), ("std", std)):
+        t = torch.as_tensor(t)
+        if t.dtype != F64 or tuple(t.shape) != (c,):
+            raise RuntimeError(f"gank: swd_project takes {name} float64 [{c}], got {tuple(t.shape)} {t.dtype}")
+        ms.append(t.cpu())
+    if not bool((ms[1] > 0).all()) or not bool(torch.isfinite(torch.cat(ms)).all()):
+        raise RuntimeError(f"gank: swd_project: mean {ms[0].tolist()} / std {ms[1].tolist()}: zero variance or not finite")
+    mean_std = torch.cat(ms).to(level.device)
+    k = c * int(nhood_size) ** 2
+    if not dirs.is_cuda:
+        raise RuntimeError("gank: dirs must live on the GPU (no CPU path exists)")
+    if dirs.dim() != 2 or dirs.dtype != F64 or dirs.shape[0] != k or dirs.shape[1] < 1:
+        raise RuntimeError(f"gank: swd_project takes dirs float64 [{k}, ndirs], got {tuple(dirs.shape)} {dirs.dtype}")
+    ndirs = dirs.shape[1]
+    out = _swd_out("swd_project", "out", out, ndirs * m, F64, level.device)
+    _lib.check(lib().gank_swd_project(_p(level, F64, "level"), n, h, w, c, _p(cx, I32, "cx"), _p(cy, I32, "cy"), m, int(nhood_size),
+                                      int(nhoods_per_image), _p(mean_std, F64, "mean_std"), _p(dirs, F64, "dirs"), ndirs, _p(out, F64, "out"),
+                                      _stream()), "swd_project")
+    return out.view(-1)[:ndirs * m].view(ndirs, m)
+
+
+def swd_sort_max_rows():
+    """the longest row `swd_sort_rows` takes"""
+    return int(lib().gank_swd_sort_max_rows())
+
+
+def swd_sort_ws_elems(dirs, m):
+    """uint32 elements of the histogram work space of `swd_sort_rows` for dirs rows of m keys"""
+    return int(dirs) * ((int(m) + 2047) // 2048) * 256
+
+
+def swd_sort_rows(keys, tmp=None, hist=None):
+    """keys float64 [dirs, M] on the device: every row sorted ascending IN PLACE by the library's own radix sort
+    (gank_swd_sort_rows); returns keys.  Finite keys of either sign, subnormals included; NaN and -0.0 are the caller's error.
+    M above swd_sort_max_rows() is refused.  tmp float64 [>= dirs * M] and hist int32 [>= swd_sort_ws_elems(dirs, M)]: work
+    space, allocated when None."""
+    if not keys.is_cuda:
+        raise RuntimeError("gank: keys must live on the GPU (no CPU path exists)")
+    if keys.dim() != 2 or keys.dtype != F64 or keys.numel() == 0:
+        raise RuntimeError(f"gank: swd_sort_rows takes float64 keys [dirs, M], got {tuple(keys.shape)} {keys.dtype}")
+    dirs, m = keys.shape
+    tmp = _swd_out("swd_sort_rows", "tmp", tmp, dirs * m, F64, keys.device)
+    hist = _swd_out("swd_sort_rows", "hist", hist, swd_sort_ws_elems(dirs, m), I32, keys.device)
+    _lib.check(lib().gank_swd_sort_rows(_p(keys, F64, "keys"), _p(tmp, F64, "tmp"), dirs, m, _p(hist, I32, "hist"), _stream()),
+               "swd_sort_rows")
+    return keys
+
+
+def swd_sorted_l1_parts(m):
+    """the workgroup partials per row gank_swd_sorted_l1 writes for rows of m keys"""
+    return (int(m) + 4095) // 4096
+
+
+def swd_sorted_l1(a, b, part=None):
+    """a, b float64 [dirs, M] on the device -> float64 [dirs, swd_sorted_l1_parts(M)] on the device: per row the workgroup
+    partials of sum_r |a[d, r] - b[d, r]| (gank_swd_sorted_l1); their sum is the caller's (common/swd.py: NumPy float64 after
+    one copy back).  part float64 [>= dirs * swd_sorted_l1_parts(M)]: the result buffer, allocated when None."""
+    for name, t in (("a", a), ("b", b)):
+        if not t.is_cuda:
+            raise RuntimeError(f"gank: {name} must live on the GPU (no CPU path exists)")
+        if t.dim() != 2 or t.dtype != F64 or t.numel() == 0:
+            raise RuntimeError(f"gank: swd_sorted_l1 takes float64 keys [dirs, M], got {name} {tuple(t.shape)} {t.dtype}")
+    if a.shape != b.shape:
+        raise RuntimeError(f"gank: swd_sorted_l1: a {tuple(a.shape)} and b {tuple(b.shape)} differ")
+    dirs, m = a.shape
+    parts = swd_sorted_l1_parts(m)
+    part = _swd_out("swd_sorted_l1", "part", part, dirs * parts, F64, a.device)
+    _lib.check(lib().gank_swd_sorted_l1(_p(a, F64, "a"), _p(b, F64, "b"), dirs, m, _p(part, F64, "part"), _stream()), "swd_sorted_l1")
+    return part.view(-1)[:dirs * parts].view(dirs, parts)
+
+
 # ------------------------------------------------------------------ profiler
 def prof_enable(on):
     lib().gank_prof_enable(int(on))

@@ -988,6 +988,50 @@ int gank_prd_counts_partial(const float* q, int nq, const float* r, int nr, int 
                             double* part_min, void* stream);
 int gank_prd_counts_finish(const int* part_count, const double* part_min, int nq, int segments, int* count, double* nearest2, void* stream);
 
+/* ---- Sliced Wasserstein distance on Laplacian-pyramid patches (common/swd.py; Karras et al., "Progressive Growing of GANs for
+ * Improved Quality, Stability, and Variation", section 5) -------------------------------------------------------------------
+ * Images and pyramid levels are float64 [N,H,W,C] on the device.  All arithmetic is float64; no atomics, every output element
+ * is written by one plain store of its sole owner: bit-identical from call to call.
+ * gank_swd_pyr_down: y [N,H/2,W/2,C] = the even rows and columns of x convolved with outer([1,4,6,4,1], [1,4,6,4,1]) / 256,
+ *   mirror boundary (index -1 -> 1, H -> H - 2).  Refused: null pointers; a side that is odd or < 4; the common rules below.
+ * gank_swd_laplacian: fine [N,H,W,C] -= pyr_up(coarse [N,H/2,W/2,C]) in place: coarse on the even positions of a zero image
+ *   of the fine size, convolved with 4 x the window, the mirror taken on that zero-stuffed grid.  Refused: as pyr_down (H, W
+ *   are the FINE sides).
+ * gank_swd_patch_stats: patch r (0 <= r < M) is the nhood x nhood x C window centred on (cy[r], cx[r]) of image
+ *   r / per_image.  part float64 [gank_swd_patch_stats_parts(M)][C][2]: per workgroup of 256 patches and per channel
+ *   sum (x - shift[c]) and sum (x - shift[c])^2 over the patches' elements (shift == NULL: 0), a thread one patch in (y, x)
+ *   order, the workgroup a fixed tree.  out float64 [C][2]: the partials added in a fixed order by a second launch.  Mean and
+ *   standard deviation are the caller's (a second call with shift = mean avoids the cancellation of sum x^2 - n mean^2).
+ * gank_swd_project: keys float64 [ndirs][M], keys[d][r] = sum over k = (c, dy, dx) of (patch_r[k] - mean_std[c]) /
+ *   mean_std[C + c] * dirs[k][d]; mean_std float64 [2 C] (means, then standard deviations), dirs float64 [K][ndirs] with
+ *   K = C nhood^2, k = (c nhood + dy) nhood + dx.  Patches are gathered from the level; the contraction is fused multiply-adds
+ *   in ascending k per key.  A standard deviation of 0 is the caller's error (it is refused on the host by common/swd.py).
+ *   Common rules of the two: refused are null pointers; sides outside 1..4096; C outside 1..16; more than 2^36 elements;
+ *   nhood even, outside 1..15 or larger than a side; M outside 1..2^24; per_image < 1 or per_image * N < M; ndirs outside
+ *   1..65535.  The centre tables are device memory the host cannot see: a centre outside [nhood / 2, side - nhood / 2) is the
+ *   caller's error (kernels.swd_patch_stats / swd_project check before upload).
+ * gank_swd_sort_rows: each of `dirs` rows of M float64 keys ascending, in place; tmp float64 [dirs][M] and hist uint32
+ *   [gank_swd_sort_ws_elems(dirs, M)] are work space.  A stable least-significant-digit radix sort, 8 passes of 8 bits on the
+ *   order-preserving transform of the key's bits; a wave owns 2048 consecutive keys, so a row need not fit a workgroup's LDS.
+ *   Contract: finite keys of either sign, subnormals included; infinities sort to the ends.  NaN (sorted by bit pattern) and
+ *   -0.0 (before +0.0) are the caller's error.  Refused: null pointers; keys == tmp; M outside 1..gank_swd_sort_max_rows()
+ *   (2^24); dirs outside 1..65535.
+ * gank_swd_sorted_l1: part float64 [dirs][gank_swd_sorted_l1_parts(M)]: per row and workgroup of 4096 keys
+ *   sum |a[d][r] - b[d][r]|, a thread 16 keys in ascending order, the workgroup a fixed tree.  The caller adds the partials
+ *   (common/swd.py: one copy back, NumPy float64).  Refused: null pointers; M, dirs as for the sort. */
+int gank_swd_pyr_down(const double* x, int N, int H, int W, int C, double* y, void* stream);
+int gank_swd_laplacian(double* fine, const double* coarse, int N, int H, int W, int C, void* stream);
+int gank_swd_patch_stats_parts(int M);
+int gank_swd_patch_stats(const double* level, int N, int H, int W, int C, const int* cx, const int* cy, int M, int nhood, int per_image,
+                         const double* shift, double* part, double* out, void* stream);
+int gank_swd_project(const double* level, int N, int H, int W, int C, const int* cx, const int* cy, int M, int nhood, int per_image,
+                     const double* mean_std, const double* dirs, int ndirs, double* keys, void* stream);
+int gank_swd_sort_max_rows(void);
+long gank_swd_sort_ws_elems(int dirs, int M);
+int gank_swd_sort_rows(double* keys, double* tmp, int dirs, int M, unsigned* hist, void* stream);
+int gank_swd_sorted_l1_parts(int M);
+int gank_swd_sorted_l1(const double* a, const double* b, int dirs, int M, double* part, void* stream);
+
 /* ---- Pix2Pix input pipeline (Pix2Pix/train.py of the reference) --------------------------------------------------------
  * gank_pix2pix_load_examples: load_examples (train.py:355-431) for a batch, one launch.  raw: uint8 [N,H,Wraw,3] on the
  *   device, 4-byte aligned.  mode 0: pair, A | B of Wraw/2 columns (:395-396); 1: multiple_A, three panels of Wraw/3, A = the
