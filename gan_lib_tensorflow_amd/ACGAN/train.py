@@ -46,7 +46,7 @@ def _g_prep_kind(name, W):
     return 0
 
 
-class ACGANTrainer(trainer.GraphTrainer):
+class ACGANTrainer(trainer.SampleMetrics, trainer.GraphTrainer):
     def __init__(self, batch_size=64, z_dim=128, acgan_scale_G=0.1, n_dis=5, max_iter=100000, device="cuda", seed=0,
                  process_group=None, state=None, use_graphs=True, allow_eager_fallback=False):
         super().__init__(device, seed, process_group, use_graphs, allow_eager_fallback)
@@ -175,103 +175,15 @@ class ACGANTrainer(trainer.GraphTrainer):
 
     global_step_counter = 0
 
-    @torch.no_grad()
-    def msssim_diversity(self, n_pairs=500, weights=None):
-        """Per-class sample diversity, the measure of the ACGAN paper: MS-SSIM (common/msssim.py of the reference) between pairs
-        of same-class samples.  Batches of `batch_size` samples on fresh noise and uniform labels (the draws of g_loss), quantised
-        as `((x + 1) * (255.99 / 2))` truncated to uint8, until every class has 2 * n_pairs samples; consecutive same-class
-        samples are paired.  -> ({class: batch MultiScaleSSIM of its n_pairs pairs}, mean over classes).  Low = diverse."""
-        from ..common.msssim import class_pair_diversity, quantize_on_device
-        set_default_store(self.store)
+    # ---- evaluation: the metrics of trainer.SampleMetrics over this hook --------------------------------------------
+    def _metric_rows(self):
+        return self.batch                # the draws of g_loss; the Inception score draws 100 (train.py:159-171)
 
-        def draw():
-            z = K.rng_normal((self.batch, self.z_dim), self.rng_state)
-            labels = K.rng_labels(self.batch, 10, self.rng_state)
-            return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3), labels
-        return class_pair_diversity(draw, n_pairs, 10, weights)
-
-    @torch.no_grad()
-    def fid(self, real, n=50000, net=None):
-        """Frechet Inception Distance (common/fid.py) between n samples and `real`: a FeatureMoments, a (mu, sigma) pair, the
-        path of an .npz with `mu` and `sigma`, or images [N,H,W,3].  Samples are the draws of `msssim_diversity` -- batches of
-        `batch_size` on fresh noise and uniform labels, quantised as `((x + 1) * (255.99 / 2))` truncated to uint8 --, mapped back
-        to [-1, 1] and fed to `net.features_f32`; samples and features never leave the device.  net: an `InceptionV3` (the frozen
-        graph's weights are a download)."""
-        from ..common.fid import calculate_fid, sample_moments
+    def _metric_batch(self, b):
+        """b samples on fresh normal noise, then fresh uniform labels (the order of g_loss), quantised as get_inception_score
+        quantises them (train.py:159-171) -> (uint8 [b, 32, 32, 3], labels [b])"""
         from ..common.msssim import quantize_on_device
         set_default_store(self.store)
-
-        def draw():
-            z = K.rng_normal((self.batch, self.z_dim), self.rng_state)
-            labels = K.rng_labels(self.batch, 10, self.rng_state)
-            return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3)
-        return calculate_fid(sample_moments(draw, n, net), real, net)
-
-    @torch.no_grad()
-    def kid(self, real, n=50000, net=None, subsets=100, subset_size=1000, seed=0):
-        """Kernel Inception Distance (common/kid.py: the unbiased polynomial-kernel MMD^2 of the pool_3 features) between n
-        samples and `real`: a FeatureBank, features [N, 2048] or images [N,H,W,3] -> (mean, std) over `subsets` subsets of
-        `subset_size` rows a side.  The samples are those of `fid`, drawn and quantised the same way; samples and features never
-        leave the device.  net: an `InceptionV3` (the frozen graph's weights are a download)."""
-        from ..common.kid import calculate_kid, sample_features
-        from ..common.msssim import quantize_on_device
-        set_default_store(self.store)
-
-        def draw():
-            z = K.rng_normal((self.batch, self.z_dim), self.rng_state)
-            labels = K.rng_labels(self.batch, 10, self.rng_state)
-            return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3)
-        return calculate_kid(sample_features(draw, n, net), real, net, subsets=subsets, subset_size=subset_size, seed=seed)
-
-    @torch.no_grad()
-    def precision_recall(self, real, n=10000, net=None, k=3):
-        """Precision, recall, density and coverage (common/precision_recall.py: k-NN manifolds of the pool_3 features) of n
-        samples against `real`: a FeatureBank, features [N, 2048] or images [N,H,W,3] -> dict(precision, recall, density,
-        coverage).  The samples are those of `kid`, drawn and quantised the same way; samples and features never leave the
-        device.  The default n is 10 000, not 50 000: in float64 a distance matrix costs 2 n^2 D FLOP per pass and there are
-        four passes, 0.41 TFLOP a pass at 10 000 and 10 TFLOP at 50 000 (25 times the time and, for the n samples, five times the
-        Inception forwards).  net: an `InceptionV3` (the frozen graph's weights are a download)."""
-        from ..common.kid import sample_features
-        from ..common.msssim import quantize_on_device
-        from ..common.precision_recall import calculate_prdc
-        set_default_store(self.store)
-
-        def draw():
-            z = K.rng_normal((self.batch, self.z_dim), self.rng_state)
-            labels = K.rng_labels(self.batch, 10, self.rng_state)
-            return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3)
-        return calculate_prdc(real, sample_features(draw, n, net), net, k)
-
-    @torch.no_grad()
-    def swd(self, real, n=8192, seed=0, **kw):
-        """Sliced Wasserstein distance on Laplacian-pyramid patches (common/swd.py; Karras et al. 2018, section 5: no network,
-        no downloaded weights) between n samples and the first n images of `real` [N >= n, 32, 32, 3] (uint8 or float32, NumPy
-        or device tensor) -> (float64 [levels], their mean), x 1000.  The samples are those of `fid`, drawn and quantised the
-        same way; they never leave the device.  **kw: nhood_size, nhoods_per_image, dir_repeats, dirs_per_repeat."""
-        from ..common.msssim import quantize_on_device
-        from ..common.swd import sample_swd
-        set_default_store(self.store)
-
-        def draw():
-            z = K.rng_normal((self.batch, self.z_dim), self.rng_state)
-            labels = K.rng_labels(self.batch, 10, self.rng_state)
-            return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3)
-        return sample_swd(draw, real, n, seed, **kw)
-
-    @torch.no_grad()
-    def inception_score(self, n=50000, net=None, splits=10):
-        """get_inception_score(n) of the training script (train.py:159-171, every evaluation_interval steps, :208-211): n / 100
-        generator passes of 100 samples on fresh normal noise and fresh uniform labels, quantised as
-        `((x + 1) * (255.99 / 2))` truncated to integers, then the Inception score in `splits` splits -> (mean, std).  On the device
-        throughout (common/inception/inception_score.py): quantisation, the map back to [-1, 1], `net.logits_device` and the
-        float64 statistics; only their final state comes back.  net: an `InceptionV3` (the frozen graph's weights are a
-        download)."""
-        from ..common.inception.inception_score import sample_inception_score
-        from ..common.msssim import quantize_on_device
-        set_default_store(self.store)
-
-        def draw():
-            z = K.rng_normal((100, self.z_dim), self.rng_state)
-            labels = K.rng_labels(100, 10, self.rng_state)
-            return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3)
-        return sample_inception_score(draw, int(n / 100), 100, net, splits)
+        z = K.rng_normal((b, self.z_dim), self.rng_state)
+        labels = K.rng_labels(b, 10, self.rng_state)
+        return quantize_on_device(self.model.get_generator(z, labels)).reshape(-1, 32, 32, 3), labels

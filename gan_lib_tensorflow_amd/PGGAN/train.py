@@ -17,7 +17,7 @@ import torch
 from .. import functional as Fn
 from .. import kernels as K
 from ..store import set_default_store
-from ..trainer import GraphTrainer
+from ..trainer import GraphTrainer, SampleMetrics
 
 
 def model_class(name):
@@ -39,7 +39,7 @@ def default_args(**over):
     return types.SimpleNamespace(**a)
 
 
-class PGGANTrainer(GraphTrainer):
+class PGGANTrainer(SampleMetrics, GraphTrainer):
     def __init__(self, args, device="cuda", seed=0, process_group=None, state=None, use_graphs=True, allow_eager_fallback=False):
         assert args.image_size == 4 * 2 ** args.block_count, "image_size must be 4 * 2**block_count (train.py:52-54)"
         super().__init__(device, seed, process_group, use_graphs, allow_eager_fallback)
@@ -131,30 +131,25 @@ class PGGANTrainer(GraphTrainer):
             z = K.rng_normal((n, self.args.z_dim), self.rng_state)
         return self.model.get_generator(z, self.alpha() if alpha is None else alpha, reuse=True)
 
+    def _metric_batch(self, b, alpha=None):
+        """the hook of trainer.SampleMetrics: `sample(b)` on fresh noise at `alpha` (default: the current fade-in weight), at the
+        stage's image_size, quantised as get_inception_score quantises (:150-162) -> (uint8 [b, size, size, 3], None: no labels)"""
+        from ..common.msssim import quantize_on_device
+        size = self.args.image_size
+        return quantize_on_device(self.sample(b, alpha=alpha)).reshape(-1, size, size, 3), None
+
     @torch.no_grad()
     def inception_score(self, n=50000, net=None, splits=10, alpha=None):
         """get_inception_score(n, alpha) of the training script (:150-162, every evaluation_interval steps at the step's fade-in
-        weight, :195-198): n / 100 generator passes of 100 samples on fresh noise at `alpha` (default: the current one), at the
-        stage's image_size -- the classifier's own bilinear resize takes them to 299 x 299 --, quantised as
-        `((x + 1) * (255.99 / 2))` truncated to integers, then the Inception score in `splits` splits -> (mean, std).  On the device
-        throughout (common/inception/inception_score.py); only the final state of the statistics comes back.  net: an
-        `InceptionV3` (the frozen graph's weights are a download)."""
+        weight, :195-198): `SampleMetrics.inception_score` on samples at `alpha` -- the classifier's own bilinear resize takes
+        them from the stage's image_size to 299 x 299."""
         from ..common.inception.inception_score import sample_inception_score
-        from ..common.msssim import quantize_on_device
-        size = self.args.image_size
-        return sample_inception_score(lambda: quantize_on_device(self.sample(100, alpha=alpha)).reshape(-1, size, size, 3), int(n / 100), 100,
-                                      net, splits)
+        return sample_inception_score(self._metric_draw(100, alpha=alpha), int(n / 100), 100, net, splits)
 
     @torch.no_grad()
     def swd(self, real, n=8192, alpha=None, seed=0, **kw):
-        """Sliced Wasserstein distance on Laplacian-pyramid patches, the metric of the progressive-GAN paper's tables (Karras et
-        al. 2018, section 5; common/swd.py: no network, no downloaded weights), between n samples and the first n images of
-        `real` [N >= n, image_size, image_size, 3] (uint8 or float32, NumPy or device tensor; already at the stage's size) ->
-        (float64 [levels], their mean), x 1000: one value per pyramid level from image_size down to 16.  The samples are those
-        of `inception_score`: generator passes of 100 on fresh noise at `alpha` (default: the current fade-in weight), quantised
-        the same way; they never leave the device.  At image_size 4 it raises: a 7 x 7 patch does not fit.
-        **kw: nhood_size, nhoods_per_image, dir_repeats, dirs_per_repeat."""
-        from ..common.msssim import quantize_on_device
+        """The metric of the progressive-GAN paper's tables: `SampleMetrics.swd` on samples at `alpha`, `real` already at the
+        stage's size; one value per pyramid level from image_size down to 16.  At image_size 4 it raises: a 7 x 7 patch does
+        not fit."""
         from ..common.swd import sample_swd
-        size = self.args.image_size
-        return sample_swd(lambda: quantize_on_device(self.sample(100, alpha=alpha)).reshape(-1, size, size, 3), real, n, seed, **kw)
+        return sample_swd(self._metric_draw(alpha=alpha), real, n, seed, **kw)

@@ -36,6 +36,7 @@ from ..common.ops import normalization as _normalization
 from ..common.ops import sn as _sn
 from ..common.ops.sn import NO_OPS
 from ..store import ParamStore, get_default_store, set_default_store
+from ..trainer import SampleMetrics
 
 BATCH_SIZE = 64  # Critic batch size                                      (:38)
 GEN_BS_MULTIPLE = 2  # Generator batch size, as a multiple of BATCH_SIZE  (:39)
@@ -341,7 +342,7 @@ class AdamTF:
         f["clean"] = True
 
 
-class SNGANTrainer:
+class SNGANTrainer(SampleMetrics):
     """One process = one GPU.  `world_size` > 1: each rank holds a full replica and its own
     BATCH_SIZE-sample shard of the real data (weak scaling) or BATCH_SIZE/world_size (strong);
     G and D gradients are summed with one RCCL all-reduce per update over the flat gradient buffer
@@ -953,16 +954,12 @@ class SNGANTrainer:
         classifier: images [-1, 1] NHWC float32 -> logits [b, >= 1000], e.g. `InceptionV3.from_npz(path).logits` (the frozen
             graph's weights are a download): the reference's host path -- samples to the host, quantised there, softmax and
             `preds2score` in NumPy;
-        net: an `InceptionV3`: the same n / 100 calls of `sample(100)`, the same draws in the same order, quantised on the
-            device, mapped back to [-1, 1] as `fid` maps them, `net.logits_device` -> `InceptionScore`
-            (common/inception/inception_score.py): samples, logits and probabilities never leave the device."""
+        net: an `InceptionV3`: the device path, `trainer.SampleMetrics.inception_score` -- the same n / 100 passes of 100, the same
+            draws in the same order, quantised on the device: samples, logits and probabilities never leave it."""
         if net is not None:
             if classifier is not None:
                 raise ValueError("inception_score: pass classifier= (the host path) or net= (the device path), not both")
-            from ..common.inception.inception_score import sample_inception_score
-            from ..common.msssim import quantize_on_device
-            return sample_inception_score(lambda: quantize_on_device(self.sample(100)).reshape(-1, 32, 32, 3), int(n / 100), 100, net,
-                                          splits, batch_size)
+            return SampleMetrics.inception_score(self, n, net, splits, batch_size)
         return _inception_score_of(self, n, classifier, splits, batch_size)
 
     def maybe_inception_score(self, classifier=None, n=50000, net=None):
@@ -981,65 +978,13 @@ class SNGANTrainer:
             labels = K.rng_labels(n, 10, self.rng_state)
         return Generator(n, labels, noise=noise, groups=1, rng_state=self.rng_state)
 
-    @torch.no_grad()
-    def msssim_diversity(self, n_pairs=500, weights=None):
-        """Per-class sample diversity (the ACGAN paper's mode-collapse measure; MS-SSIM is an evaluation TODO of the reference's
-        README, common/msssim.py): samples come through the IS sampling path -- `sample(100)` on fresh uniform labels, so the
-        conditional batch norm sees the mixed-label batch statistics it sees everywhere else --, quantised on the device as for
-        the score (:551), until every class has 2 * n_pairs of them; consecutive same-class samples are paired.
-        -> ({class: batch MultiScaleSSIM of its n_pairs pairs}, mean over classes).  Low = diverse."""
-        from ..common.msssim import class_pair_diversity, quantize_on_device
-
-        def draw():
-            labels = K.rng_labels(100, 10, self.rng_state)
-            return quantize_on_device(self.sample(100, labels)).reshape(-1, 32, 32, 3), labels
-        return class_pair_diversity(draw, n_pairs, 10, weights)
-
-    @torch.no_grad()
-    def fid(self, real, n=50000, net=None):
-        """Frechet Inception Distance (the FID column / TODO of the reference's README; common/fid.py) between n samples and
-        `real`: a FeatureMoments, a (mu, sigma) pair, the path of an .npz with `mu` and `sigma`, or images [N,H,W,3].  Samples come
-        through the IS sampling path -- n / 100 calls of `sample(100)` on fresh uniform labels --, are quantised on the device as
-        for the score (:551), mapped back to [-1, 1] and fed to `net.features_f32`; samples and features never leave the device.
-        net: an `InceptionV3` (the frozen graph's weights are a download)."""
-        from ..common.fid import calculate_fid, sample_moments
+    def _metric_batch(self, b):
+        """the hook of trainer.SampleMetrics: fresh uniform labels, then `sample(b, labels)` -- the draws of `sample(b)`, the IS
+        sampling path, so the conditional batch norm sees the mixed-label batch statistics it sees everywhere else --,
+        quantised as for the score (:551) -> (uint8 [b, 32, 32, 3], labels [b])"""
         from ..common.msssim import quantize_on_device
-        return calculate_fid(sample_moments(lambda: quantize_on_device(self.sample(100)).reshape(-1, 32, 32, 3), n, net), real, net)
-
-    @torch.no_grad()
-    def kid(self, real, n=50000, net=None, subsets=100, subset_size=1000, seed=0):
-        """Kernel Inception Distance (common/kid.py: the unbiased polynomial-kernel MMD^2 of the pool_3 features) between n
-        samples and `real`: a FeatureBank, features [N, 2048] or images [N,H,W,3] -> (mean, std) over `subsets` subsets of
-        `subset_size` rows a side.  The samples are those of `fid`, drawn and quantised the same way; samples and features never
-        leave the device.  net: an `InceptionV3` (the frozen graph's weights are a download)."""
-        from ..common.kid import calculate_kid, sample_features
-        from ..common.msssim import quantize_on_device
-        bank = sample_features(lambda: quantize_on_device(self.sample(100)).reshape(-1, 32, 32, 3), n, net)
-        return calculate_kid(bank, real, net, subsets=subsets, subset_size=subset_size, seed=seed)
-
-    @torch.no_grad()
-    def precision_recall(self, real, n=10000, net=None, k=3):
-        """Precision, recall, density and coverage (common/precision_recall.py: k-NN manifolds of the pool_3 features) of n
-        samples against `real`: a FeatureBank, features [N, 2048] or images [N,H,W,3] -> dict(precision, recall, density,
-        coverage).  The samples are those of `kid`, drawn and quantised the same way; samples and features never leave the
-        device.  The default n is 10 000, not 50 000: in float64 a distance matrix costs 2 n^2 D FLOP per pass and there are
-        four passes, 0.41 TFLOP a pass at 10 000 and 10 TFLOP at 50 000 (25 times the time and, for the n samples, five times the
-        Inception forwards).  net: an `InceptionV3` (the frozen graph's weights are a download)."""
-        from ..common.kid import sample_features
-        from ..common.msssim import quantize_on_device
-        from ..common.precision_recall import calculate_prdc
-        bank = sample_features(lambda: quantize_on_device(self.sample(100)).reshape(-1, 32, 32, 3), n, net)
-        return calculate_prdc(real, bank, net, k)
-
-    @torch.no_grad()
-    def swd(self, real, n=8192, seed=0, **kw):
-        """Sliced Wasserstein distance on Laplacian-pyramid patches (common/swd.py; Karras et al. 2018, section 5: no network,
-        no downloaded weights) between n samples and the first n images of `real` [N >= n, 32, 32, 3] (uint8 or float32, NumPy
-        or device tensor) -> (float64 [levels], their mean), x 1000.  The samples are those of `fid`, drawn and quantised the
-        same way; they never leave the device.  **kw: nhood_size, nhoods_per_image, dir_repeats, dirs_per_repeat."""
-        from ..common.msssim import quantize_on_device
-        from ..common.swd import sample_swd
-        return sample_swd(lambda: quantize_on_device(self.sample(100)).reshape(-1, 32, 32, 3), real, n, seed, **kw)
+        labels = K.rng_labels(b, 10, self.rng_state)
+        return quantize_on_device(self.sample(b, labels)).reshape(-1, 32, 32, 3), labels
 
 
 def _inception_score_of(trainer, n, classifier, splits, batch_size):

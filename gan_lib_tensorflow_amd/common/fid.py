@@ -130,14 +130,24 @@ def image_moments(images, net, batch_size=100):
     return mom
 
 
+def draw_until(draw, n):
+    """The batches of n generated rows: draw() -> a batch [b >= 1, ...] is called while rows are missing and the last batch is
+    cut to the rows still needed.  draw() is never called once n rows are in: a call advances the device RNG."""
+    have = 0
+    while have < n:
+        batch = draw()[:n - have]
+        have += len(batch)
+        yield batch
+
+
 def sample_moments(draw, n, net):
     """FeatureMoments of n generated samples: draw() -> uint8 images [b,H,W,3] on the device, quantised as for the Inception
-    score (msssim.quantize_on_device), called until n are in; samples and features stay on the device"""
+    score (msssim.quantize_on_device), called until n are in (`draw_until`); samples and features stay on the device"""
     if net is None:
         raise NotImplementedError(_NO_WEIGHTS)
     mom = FeatureMoments(2048, net.device)
-    while mom.count < n:
-        mom.update(net.features_f32(_unit_range(draw()[:n - mom.count])))
+    for batch in draw_until(draw, n):
+        mom.update(net.features_f32(_unit_range(batch)))
     return mom
 
 

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .. import kernels as K
-from .fid import _NO_WEIGHTS, _unit_range
+from .fid import _NO_WEIGHTS, _unit_range, draw_until
 
 
 class FeatureBank:
@@ -86,8 +86,8 @@ def sample_features(draw, n, net):
     if net is None:
         raise NotImplementedError(_NO_WEIGHTS)
     bank = FeatureBank(2048, n, net.device)
-    while bank.count < n:
-        bank.append(net.features_f32(_unit_range(draw()[:n - bank.count])))
+    for batch in draw_until(draw, n):
+        bank.append(net.features_f32(_unit_range(batch)))
     return bank
 
 

@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from .. import kernels as K
+from .fid import draw_until
 
 
 def level_sizes(h, w):
@@ -170,7 +171,7 @@ def calculate_swd(a, b, nhood_size=7, nhoods_per_image=128, dir_repeats=4, dirs_
 
 def sample_swd(draw, real, n, seed=0, nhood_size=7, **kw):
     """SWD of n generated samples against the first n images of `real` [N >= n,H,W,C]: draw() -> uint8 images [b,H,W,C] on the
-    device, called until n are in (the loop of fid.sample_moments); the samples stay on the device.  A patch that does not fit
+    device, called until n are in (fid.draw_until); the samples stay on the device.  A patch that does not fit
     the images raises before anything is drawn.  **kw: nhoods_per_image, dir_repeats, dirs_per_repeat of `calculate_swd`."""
     if getattr(real, 'ndim', 0) != 4:
         raise ValueError(f"swd: real {tuple(getattr(real, 'shape', ()))}, expected images [N,H,W,C]")
@@ -178,11 +179,7 @@ def sample_swd(draw, real, n, seed=0, nhood_size=7, **kw):
         raise ValueError(f"swd: real has {len(real)} images, needs at least {n}")
     if nhood_size > min(level_sizes(real.shape[1], real.shape[2])[-1]):
         raise ValueError(f"swd: a {nhood_size} x {nhood_size} patch does not fit {real.shape[1]} x {real.shape[2]} images")
-    batches, have = [], 0
-    while have < n:
-        batches.append(draw()[:n - have])
-        have += len(batches[-1])
-    fake = torch.cat(batches)
+    fake = torch.cat(list(draw_until(draw, n)))
     if tuple(fake.shape[1:]) != tuple(real.shape[1:]):
         raise ValueError(f"swd: real {tuple(real.shape)} is not at the samples' size {tuple(fake.shape[1:])}")
     return calculate_swd(fake, real[:n], nhood_size=nhood_size, seed=seed, **kw)

@@ -13,12 +13,9 @@
 // element, there is no split over i and there are no atomics, so two calls on the same data give the same bits.  Tiles
 // strictly below the diagonal (possible only in a diagonal workgroup) and tiles past D are neither read nor written.  The
 // column sums are taken by the diagonal workgroups from the staged panel, one thread per column, in index order.
-#include "gank_common.h"
+#include "f64_tile.h"
 
 namespace {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kFidThreads = 256;
 constexpr int kFidBlock = 64;      // gram rows / columns per workgroup

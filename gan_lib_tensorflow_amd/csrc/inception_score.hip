@@ -18,29 +18,14 @@
 //                global row order, so the same rows fed in calls of any sizes leave the same bits: state after a call is
 //                (..((state + t_0) + t_1).. + t_k), whichever call t_i arrived in.  No atomics, no partial sums per call.
 // The parallelism is over columns x splits (a wave per 64 columns), not over rows: 100 x 1000 float64 exp per call.
-#include "gank_common.h"
+#include "f64_tile.h"
 
 namespace {
 
 constexpr int kIsClasses = 1000;               // the first 1000 of the frozen graph's 1008 logits (inception_score.py:55)
 constexpr int kIsState = kIsClasses + 1;       // + the scalar sum_x sum_y p (l - lse)
-constexpr int kIsRowThreads = 256;
+constexpr int kIsRowThreads = kF64Threads;     // block_sum (f64_tile.h) is the sum over 256 threads
 constexpr int kIsColThreads = 64;
-
-__device__ __forceinline__ double is_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// sum over the workgroup's 256 threads, the same bits in every thread; `red` holds 4 doubles
-__device__ __forceinline__ double is_block_sum(double v, double* red) {
-  v = is_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 __global__ __launch_bounds__(kIsRowThreads) void is_row_kernel(const float* __restrict__ logits, int ld, double* __restrict__ scratch) {
   __shared__ double red[4];
@@ -56,13 +41,13 @@ __global__ __launch_bounds__(kIsRowThreads) void is_row_kernel(const float* __re
   const double mx = (double)fmaxf(fmaxf(redm[0], redm[1]), fmaxf(redm[2], redm[3]));
   double s = 0.0;
   for (int y = tid; y < kIsClasses; y += kIsRowThreads) s += exp((double)row[y] - mx);
-  const double lse = mx + log(is_block_sum(s, red));
+  const double lse = mx + log(block_sum(s, red));
   double e = 0.0;
   for (int y = tid; y < kIsClasses; y += kIsRowThreads) {
     const double d = (double)row[y] - lse;
     e += exp(d) * d;              // exp underflows to 0 long before d reaches -inf: 0 * finite, never 0 * -inf
   }
-  e = is_block_sum(e, red);
+  e = block_sum(e, red);
   if (tid == 0) {
     scratch[2 * (size_t)r] = lse;
     scratch[2 * (size_t)r + 1] = e;

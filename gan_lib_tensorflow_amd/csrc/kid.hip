@@ -12,57 +12,31 @@
 // (T = ceil(m / 64)); partial[s][blockIdx.x] is that tile's sum, so a subset's row of `partial` is 2 tri + T * T long and its
 // three blocks start at 0, tri and 2 tri.
 //
-// Staging.  The contraction runs over the FEATURE axis: A[i][k] = x[ix[s][r0 + i]][k0 + k], B[k][j] = y[iy[s][c0 + j]][k0 + k].
+// Dot products.  The contraction runs over the FEATURE axis: A[i][k] = x[ix[s][r0 + i]][k0 + k], B[k][j] = y[iy[s][c0 + j]][k0 + k].
 // The workgroup gathers its 64 + 64 rows through the tables (each thread resolves its four row pointers once; positions past
-// m re-read position m - 1 and are masked in the epilogue) and stages them in chunks of 32 features as fs[side][row][k],
-// widened to float64 (exact), features past D as zeros; the next chunk's global loads are in flight while the current one is
-// multiplied.  The f64 MFMA's operand map is: lane l holds A[l & 15][l >> 4] and B[l >> 4][l & 15], four contraction steps per
-// instruction, one per value of l >> 4.  Which feature a step stands for is free as long as A and B agree, so a lane reads
-// the PAIR of features fs[side][q0 + (l & 15)][8 kg + 2 (l >> 4) + {0, 1}] with one 16-byte LDS read and feeds element 0 to one
-// MFMA (features 8 kg + {0, 2, 4, 6}) and element 1 to the next (8 kg + {1, 3, 5, 7}): half the LDS instructions of one read
-// per MFMA operand.  The result map is the f64 one, col = l & 15, row = (l >> 4) + 4 * reg (NOT the fp32 map).
-//
-// The LDS pitch.  A ds_read_b128 is served in four groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the
-// same + 32 -- and a lane takes the 4 banks (2 e) mod 64 .. + 3 of its first double's index e, so a group is conflict-free
-// when its 16 values of (e / 2) mod 16 differ.  Here e / 2 = (l & 15) * pitch / 2 + (l >> 4) + const.  With pitch = 36,
-// pitch / 2 = 18 = 2 (mod 16): the first group holds rows {0-3, 12-15} of one l >> 4, residues 2 i = the 8 even ones, and rows
-// 4-11 of the next l >> 4, residues 2 i + 1 = the 8 odd ones; the second group the same with the roles swapped: 16 distinct
-// residues each.  (The 80 of fid.hip serves 8-byte reads ALONG a staged row, the row fixed per half-wave; here the row varies
-// with the lane and 80 / 2 = 8 (mod 16) would put rows i and i + 2 on one bank.)  36 * 8 bytes is a multiple of 16, so the
-// 16-byte reads and staging stores are aligned.
+// m re-read position m - 1 and are masked in the epilogue) and hands them to f64_tile_dots (f64_tile.h: the staging in chunks
+// of 32 features widened to float64, the f64 MFMA's operand map and the conflict-free LDS pitch are documented there).
 //
 // Epilogue, float64: t = gamma * dot + coef0, t^degree by repeated multiplication, the masks (row or column >= m; i == j in a
-// diagonal tile of XX / YY), then a sum in a fixed order: the lane's 16 elements in register order, an xor butterfly over the
-// 64 lanes (32, 16, .., 1), the four waves through LDS and thread 0 adding them in index order; one plain store.  No atomics,
-// no split of the contraction: two calls on the same data return the same bits.
-#include "gank_common.h"
+// diagonal tile of XX / YY), then a sum in a fixed order: the lane's 16 elements in register order, then block_sum
+// (f64_tile.h: an xor butterfly over the 64 lanes, the four waves through LDS, added in index order); one plain store by
+// thread 0.  No atomics, no split of the contraction: two calls on the same data return the same bits.
+#include "f64_tile.h"
 
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kKidThreads = 256;
-constexpr int kKidTile = 64;       // rows / columns of the kernel matrix per workgroup
-constexpr int kKidChunk = 32;      // features per staged chunk
-constexpr int kKidPitch = 36;     // doubles per staged row (header: why it is conflict-free)
-constexpr int kKidItems = 2 * kKidTile * (kKidChunk / 4) / kKidThreads;     // 4-feature staging items per thread and chunk
+constexpr int kKidThreads = kF64Threads;
+constexpr int kKidTile = kF64Tile;         // rows / columns of the kernel matrix per workgroup
 constexpr int kKidMaxM = 65536;    // T <= 1024: 2 tri + T * T fits gridDim.x and an int
 constexpr int kKidMaxSubsets = 65535;      // gridDim.y
 
 __host__ __device__ inline int kid_tiles(int m) { return (m + kKidTile - 1) / kKidTile; }
 
-__device__ __forceinline__ double kid_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(kKidThreads) void kid_block_sums_kernel(const float* __restrict__ x, const float* __restrict__ y, int D,
                                                                      const int* __restrict__ ix, const int* __restrict__ iy, int m,
                                                                      double gamma, double coef0, int degree,
                                                                      double* __restrict__ partial) {
-  __shared__ __attribute__((aligned(16))) double fs[2][kKidTile][kKidPitch];
+  __shared__ __attribute__((aligned(16))) double fs[kF64StageDoubles];
   __shared__ double red[4];
   const int T = kid_tiles(m), tri = T * (T + 1) / 2;
   int t = blockIdx.x, block = 0;                      // block 0: XX, 1: YY, 2: XY
@@ -81,12 +55,12 @@ __global__ __launch_bounds__(kKidThreads) void kid_block_sums_kernel(const float
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wr = w >> 1, wc = w & 1;
 
-  // staging item q of this thread: row (tid >> 3) + 32 q of the 128 staged rows (side 0: the tile's rows, side 1: its columns),
-  // 4 features from c4 of the chunk
+  // staging item q of this thread (f64_tile.h): row (tid >> 3) + 32 q of the 128 staged rows (side 0: the tile's rows, side 1:
+  // its columns), 4 features from c4 of the chunk
   const int c4 = (tid & 7) * 4;
-  const float* src[kKidItems];
+  const float* src[kF64Items];
 #pragma unroll
-  for (int q = 0; q < kKidItems; q++) {
+  for (int q = 0; q < kF64Items; q++) {
     const int r = (tid >> 3) + 32 * q, side = r >> 6;
     int pos = (side ? bj : bi) * kKidTile + (r & (kKidTile - 1));
     pos = pos < m ? pos : m - 1;
@@ -94,51 +68,8 @@ __global__ __launch_bounds__(kKidThreads) void kid_block_sums_kernel(const float
     const int row = (from_y ? iy : ix)[(size_t)s * m + pos];
     src[q] = (from_y ? y : x) + (size_t)row * D + c4;
   }
-  f32x4 raw[kKidItems];
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < kKidItems; q++) {
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (k0 + c4 < D) v = *reinterpret_cast<const f32x4*>(src[q] + k0);      // D % 16 == 0: k0 + c4 < D covers k0 + c4 + 3
-      raw[q] = v;
-    }
-  };
-
   f64x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 2; j++) acc[i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
-
-  fetch(0);
-  for (int k0 = 0; k0 < D; k0 += kKidChunk) {
-#pragma unroll
-    for (int q = 0; q < kKidItems; q++) {
-      const int r = (tid >> 3) + 32 * q;
-      f64x2* dst = reinterpret_cast<f64x2*>(&fs[r >> 6][r & (kKidTile - 1)][c4]);
-      dst[0] = f64x2{(double)raw[q][0], (double)raw[q][1]};
-      dst[1] = f64x2{(double)raw[q][2], (double)raw[q][3]};
-    }
-    __syncthreads();
-    if (k0 + kKidChunk < D) fetch(k0 + kKidChunk);
-#pragma unroll
-    for (int kg = 0; kg < kKidChunk / 8; kg++) {
-      const int k = kg * 8 + 2 * (lane >> 4);         // this lane's feature pair of the group of 8
-      f64x2 a[2], b[2];
-#pragma unroll
-      for (int i = 0; i < 2; i++) {
-        a[i] = *reinterpret_cast<const f64x2*>(&fs[0][wr * 32 + i * 16 + (lane & 15)][k]);
-        b[i] = *reinterpret_cast<const f64x2*>(&fs[1][wc * 32 + i * 16 + (lane & 15)][k]);
-      }
-#pragma unroll
-      for (int e = 0; e < 2; e++)
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-          for (int j = 0; j < 2; j++) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i][e], b[j][e], acc[i][j], 0, 0, 0);
-    }
-    __syncthreads();
-  }
+  f64_tile_dots(src, D, fs, acc, F64NoStagingHook());
 
   const bool diagonal = block < 2 && bi == bj;
   double sum = 0.0;
@@ -158,11 +89,8 @@ __global__ __launch_bounds__(kKidThreads) void kid_block_sums_kernel(const float
       }
     }
   }
-  sum = kid_wave_sum(sum);
-  if (lane == 0) red[w] = sum;
-  __syncthreads();
+  double total = block_sum(sum, red);
   if (tid == 0) {
-    double total = ((red[0] + red[1]) + red[2]) + red[3];
     if (block < 2 && bi < bj) total *= 2.0;           // the mirror tile (bj, bi) has no workgroup
     partial[(size_t)s * gridDim.x + blockIdx.x] = total;
   }
@@ -176,7 +104,7 @@ __global__ __launch_bounds__(64) void kid_finish_kernel(const double* __restrict
   const double* p = partial + (size_t)s * (2 * tri + T * T) + block * tri;
   double v = 0.0;
   for (int t = lane; t < count; t += 64) v += p[t];
-  v = kid_wave_sum(v);
+  v = wave_sum(v);
   if (lane == 0) out[(size_t)s * 3 + block] = v;
 }
 

@@ -10,16 +10,14 @@
 // Decomposition.  A 256-thread workgroup owns a strip of 64 rows (blockIdx.x) and walks the 64-column tiles of one column
 // segment (blockIdx.y): the T = ceil(n / 64) column tiles are cut into `segments` contiguous ranges, segment s = tiles
 // [T s / segments, T (s + 1) / segments), so that a small n still fills the chip.  The full matrix is computed, also bank
-// against itself.  Per tile the dot products are the tile loop of kid.hip: the contraction over the feature axis on
-// v_mfma_f64_16x16x4_f64, the four waves a 32 x 32 quadrant each; the 64 + 64 rows staged in chunks of 32 features as
-// fs[side][row][k] widened to float64, pitch 36 doubles, a lane reading a PAIR of features with one 16-byte LDS read for two
-// consecutive MFMAs -- the staging, the pitch argument and the operand map are documented at the top of kid.hip.  The result
-// map is the f64 one, col = l & 15, row = (l >> 4) + 4 * reg (NOT the fp32 map).  Rows and columns past the end re-read the last
-// row and are masked below.
+// against itself.  Per tile the dot products are f64_tile_dots (f64_tile.h, shared with kid.hip: the contraction over the
+// feature axis on v_mfma_f64_16x16x4_f64, the four waves a 32 x 32 quadrant each; the staging, the LDS pitch and the operand
+// map are documented there).  The result map is the f64 one, col = l & 15, row = (l >> 4) + 4 * reg (NOT the fp32 map).  Rows and
+// columns past the end re-read the last row and are masked below.
 //
-// Norms.  A staging thread squares the 4 features it has just widened and adds them to a float64 partial of its row (the
-// products of float32 values are exact); 8 consecutive lanes stage one row, an xor butterfly (1, 2, 4) adds their partials after
-// the last chunk.  The order is fixed, so a row's norm is the same bits in whichever workgroup computes it.  The strip's own
+// Norms.  Through the staging hook of f64_tile_dots a staging thread squares the 4 features it has just widened and adds them
+// to a float64 partial of its row (the products of float32 values are exact); 8 consecutive lanes stage one row, an xor
+// butterfly (1, 2, 4) adds their partials after the last chunk.  The order is fixed, so a row's norm is the same bits in whichever workgroup computes it.  The strip's own
 // norms are formed during the segment's first tile only.
 //
 // Epilogue.  The staging buffer is free after the last chunk; the waves store their dot products there as a 64 x 64 tile, pitch
@@ -35,23 +33,17 @@
 //           the four classes add / min by xor shuffles -> part_count[row][segment], part_min[row][segment].
 // The k smallest of a set and an integer sum do not depend on the order or on the cut into segments; no atomics, no split of
 // the contraction: two calls on the same data, with any segment counts, return the same bits.
-#include "gank_common.h"
+#include "f64_tile.h"
 
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kPrdThreads = 256;
-constexpr int kPrdTile = 64;       // rows per strip / columns per tile
-constexpr int kPrdChunk = 32;      // features per staged chunk
-constexpr int kPrdPitch = 36;      // doubles per staged row (kid.hip: why it is conflict-free)
+constexpr int kPrdThreads = kF64Threads;
+constexpr int kPrdTile = kF64Tile;         // rows per strip / columns per tile
 constexpr int kPrdD2Pitch = 68;    // doubles per row of the tile of dot products (header)
-constexpr int kPrdItems = 2 * kPrdTile * (kPrdChunk / 4) / kPrdThreads;     // 4-feature staging items per thread and chunk
 constexpr int kPrdMaxK = 8;
 constexpr int kPrdMaxRows = 1 << 24;       // ceil(n / 64) fits gridDim.x with room, n * 64 an int
 constexpr int kPrdMaxSegments = 65535;     // gridDim.y
-static_assert(kPrdTile * kPrdD2Pitch <= 2 * kPrdTile * kPrdPitch, "the tile of dot products lives in the staging buffer");
+static_assert(kPrdTile * kPrdD2Pitch <= kF64StageDoubles, "the tile of dot products lives in the staging buffer");
 
 __host__ __device__ inline int prd_tiles(int n) { return (n + kPrdTile - 1) / kPrdTile; }
 __host__ __device__ inline int prd_segment_begin(int T, int segments, int s) { return (int)((long long)T * s / segments); }
@@ -71,7 +63,7 @@ template <bool kRadii>
 __global__ __launch_bounds__(kPrdThreads) void prd_strip_kernel(const float* __restrict__ a, int na, const float* __restrict__ b, int nb, int D,
                                                                 const double* __restrict__ radii2, int k, int segments,
                                                                 double* __restrict__ part, int* __restrict__ part_count) {
-  __shared__ __attribute__((aligned(16))) double buf[2 * kPrdTile * kPrdPitch];      // fs[side][row][k], then dots[row][col]
+  __shared__ __attribute__((aligned(16))) double buf[kF64StageDoubles];      // fs[side][row][k], then dots[row][col]
   __shared__ double norm[2][kPrdTile];
   __shared__ double rad[kPrdTile];
   const int T = prd_tiles(nb), bi = blockIdx.x, seg = blockIdx.y;
@@ -89,69 +81,28 @@ __global__ __launch_bounds__(kPrdThreads) void prd_strip_kernel(const float* __r
   double nearest = INFINITY;
 
   for (int bj = t0; bj < t1; bj++) {
-    const float* src[kPrdItems];
+    const float* src[kF64Items];
 #pragma unroll
-    for (int q = 0; q < kPrdItems; q++) {
+    for (int q = 0; q < kF64Items; q++) {
       const int r = (tid >> 3) + 32 * q, side = r >> 6;
       int pos = (side ? bj : bi) * kPrdTile + (r & (kPrdTile - 1));
       const int last = (side ? nb : na) - 1;
       pos = pos < last ? pos : last;
       src[q] = (side ? b : a) + (size_t)pos * D + c4;
     }
-    f32x4 raw[kPrdItems];
-    auto fetch = [&](int k0) {
+    double sq[kF64Items];
 #pragma unroll
-      for (int q = 0; q < kPrdItems; q++) {
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (k0 + c4 < D) v = *reinterpret_cast<const f32x4*>(src[q] + k0);      // D % 16 == 0: k0 + c4 < D covers k0 + c4 + 3
-        raw[q] = v;
-      }
-    };
-    double sq[kPrdItems];
-    f64x4 acc[2][2];
-#pragma unroll
-    for (int q = 0; q < kPrdItems; q++) sq[q] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < 2; j++) acc[i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
+    for (int q = 0; q < kF64Items; q++) sq[q] = 0.0;
     const bool first = bj == t0;                      // the strip's own norms are formed once
-
-    fetch(0);
-    for (int k0 = 0; k0 < D; k0 += kPrdChunk) {
-#pragma unroll
-      for (int q = 0; q < kPrdItems; q++) {
-        const int r = (tid >> 3) + 32 * q;
-        const double d0 = raw[q][0], d1 = raw[q][1], d2 = raw[q][2], d3 = raw[q][3];
-        f64x2* dst = reinterpret_cast<f64x2*>(&buf[r * kPrdPitch + c4]);
-        dst[0] = f64x2{d0, d1};
-        dst[1] = f64x2{d2, d3};
-        if (r >= kPrdTile || first) sq[q] = (((sq[q] + d0 * d0) + d1 * d1) + d2 * d2) + d3 * d3;
-      }
-      __syncthreads();
-      if (k0 + kPrdChunk < D) fetch(k0 + kPrdChunk);
-#pragma unroll
-      for (int kg = 0; kg < kPrdChunk / 8; kg++) {
-        const int kk = kg * 8 + 2 * (lane >> 4);      // this lane's feature pair of the group of 8
-        f64x2 fa[2], fb[2];
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-          fa[i] = *reinterpret_cast<const f64x2*>(&buf[(wr * 32 + i * 16 + (lane & 15)) * kPrdPitch + kk]);
-          fb[i] = *reinterpret_cast<const f64x2*>(&buf[(kPrdTile + wc * 32 + i * 16 + (lane & 15)) * kPrdPitch + kk]);
-        }
-#pragma unroll
-        for (int e = 0; e < 2; e++)
-#pragma unroll
-          for (int i = 0; i < 2; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[i][e], fb[j][e], acc[i][j], 0, 0, 0);
-      }
-      __syncthreads();
-    }
+    f64x4 acc[2][2];
+    f64_tile_dots(src, D, buf, acc, [&](int q, double d0, double d1, double d2, double d3) {
+      const int r = (tid >> 3) + 32 * q;
+      if (r >= kPrdTile || first) sq[q] = (((sq[q] + d0 * d0) + d1 * d1) + d2 * d2) + d3 * d3;
+    });
 
     // the staging buffer is free: norms, the tile's radii and the dot products go to LDS
 #pragma unroll
-    for (int q = 0; q < kPrdItems; q++) {
+    for (int q = 0; q < kF64Items; q++) {
       const int r = (tid >> 3) + 32 * q;
       if (r >= kPrdTile || first) {                   // uniform over the wave: all 8 lanes of a row take part
         double v = sq[q];
