@@ -1,8 +1,23 @@
-"""ctypes binding of libgank.so (include/gank.h).  There is NO fallback: if the HIP library is
-missing or a symbol is absent this module raises, and every compute entry point of the package
-goes through it."""
+"""ctypes binding of libgank.so, derived from include/gank.h at import.  There is NO fallback: if the HIP library is
+missing or a symbol is absent this module raises, and every compute entry point of the package goes through it.
+
+The header is the only description of the ABI: parse_header() reads its `#define GANK_*` constants, its descriptor structs and
+every function declaration, and nothing here names a symbol or a field.  To add an entry point, declare it in gank.h, define it
+in csrc/, wrap it in kernels.py.  The typing rules:
+  - by value: int, long, long long, float, double, int64_t -- any other spelling is a RuntimeError at import that names the
+    declaration (so is anything else the reader cannot read: it never skips);
+  - returns: int, long, double, const char* (c_char_p);
+  - a pointer to one of the header's structs: POINTER(that Structure) -- callers pass (Struct * n)() arrays and byref(struct), and
+    a descriptor of the wrong kind is refused;
+  - every other pointer, struct fields included: c_void_p, which takes tensor addresses, None, byref(c_int / c_double),
+    (c_float * n)(), (c_void_p * n)() and string buffers alike.  The element type of such a pointer is NOT checked.  That is
+    looser than the hand-kept table this replaces in twelve places, which were POINTER(c_int / c_float / c_double / c_void_p)
+    or c_char_p there: the double*, int* and char* outputs of gank_prof_collect and gank_prof_kernel_stats, the window of
+    gank_msssim_level, prep_weight of gank_sn_power_iter_fwd_prep / _fwd_b_prep / _fwd_b_prep_feed and u_next of
+    gank_sn_adam_fwd_a (and tighter in one: the job table of gank_sum_slabs_label_bwd is POINTER(SlabJob) as the header says)."""
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GANK_DTYPE = bf16 (default) | fp16: the element type of activations / MFMA operands for this PROCESS.  The two are separate
@@ -14,257 +29,74 @@ if DTYPE not in ("bf16", "fp16"):
 ACT_DTYPE_NAME = "bfloat16" if DTYPE == "bf16" else "float16"
 LIB_PATH = os.path.join(_HERE, os.environ.get("GANK_LIB_NAME", "libgank.so" if DTYPE == "bf16" else "libgank_f16.so"))   # GANK_LIB_NAME: experiment builds
 
-P, I, L, F = C.c_void_p, C.c_int, C.c_long, C.c_float
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "gank.h")
 
-# flags (include/gank.h)
-IN_UPSAMPLE2X, IN_RELU, OUT_TANH, DY_UPSAMPLE2X, RES_UPSAMPLE2X, STATS_PREZEROED, OUT_POOLSUM2X = 1, 2, 4, 8, 64, 256, 512
-STAT_SLOTS = 16   # GANK_STAT_SLOTS
-
-
-class SnDesc(C.Structure):
-    """gank_sn_desc"""
-    _fields_ = [(n, P) for n in ("W", "u_in", "u_out", "v", "W_bar", "scal", "a", "b", "bpart",
-                                 "dW_bar", "dW", "rowdot", "ga", "u_snap")] + \
-               [("K", I), ("C", I), ("row_offset", I), ("chunk_offset", I)]
+# every C type the header may spell by value; anything else fails the import with the declaration's name
+_SCALARS = {"int": C.c_int, "long": C.c_long, "long long": C.c_longlong, "float": C.c_float, "double": C.c_double, "int64_t": C.c_int64}
+_RETURNS = {"int": C.c_int, "long": C.c_long, "double": C.c_double, "const char*": C.c_char_p}
 
 
-class WgradItem(C.Structure):
-    """gank_wgrad_item"""
-    _fields_ = [("x", P), ("dy", P), ("dw", P), ("dbias", P)]
+def _ctype(decl, owner, structs):
+    """One `type name` declaration (a function argument or a struct field) of `owner` -> (name, ctype)."""
+    *kind, name = [w for w in re.findall(r"\w+|\S", decl) if w != "const"] or [""]
+    if re.fullmatch(r"[A-Za-z_]\w*", name) and name not in kind:        # (`long long` without a name is not `long` called long)
+        if re.fullmatch(r"\w+( \w+)*( \*)+", " ".join(kind)):
+            return name, C.POINTER(structs[kind[0]]) if kind[0] in structs and len(kind) == 2 else C.c_void_p
+        if " ".join(kind) in _SCALARS:
+            return name, _SCALARS[" ".join(kind)]
+    raise RuntimeError(f"gank.h: {owner}: cannot type {' '.join(decl.split())!r}")
 
 
-class SlabJob(C.Structure):
-    """gank_slab_job"""
-    _fields_ = [("slabs", P), ("out", P), ("n", L), ("stride", L), ("nslabs", I), ("scale", F), ("fold", I), ("out_run", L), ("out_pitch", L)]
+def parse_header(text):
+    """C header text -> (defines, structs, prototypes, returns): the `#define GANK_*` integers by name, one ctypes.Structure per
+    `typedef struct ... { ... } gank_x;` by its C name, and the argtypes and the restype of every declared function by symbol."""
+    def bad(decl, why):
+        symbol = (re.findall(r"\bgank_\w+", decl, flags=re.I) or ["?"])[0]
+        return RuntimeError(f"gank.h: {symbol}: {why}: {' '.join(decl.split())[:100]!r}")
+
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    expected = len(re.findall(r"\bgank_[a-z0-9_]+\s*\(", text))
+    defines = {}
+    for line in re.findall(r"^[ \t]*#[ \t]*define[ \t]+GANK_\w+[ \t]+\S.*$", text, flags=re.M):     # (the include guard has no value)
+        try:
+            defines[line.split()[1]] = int(line.split(None, 2)[2], 0)
+        except ValueError:
+            raise bad(line, "not an integer constant") from None
+    text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{', " ", text, flags=re.M)
+    structs = {}
+
+    def struct(m):
+        fields = []
+        for decl in filter(None, (d.strip() for d in m.group(1).split(";"))):
+            first, *more = decl.split(",")      # `int ksize, Cin, Cout;`: the type is what stands before the first name (or star)
+            base = first.split("*")[0] if "*" in first else re.sub(r"\w+\s*$", "", first)
+            fields += [_ctype(d, m.group(2), {}) for d in [first] + [base + " " + d for d in more]]
+        camel = "".join(w.capitalize() for w in m.group(2).split("_")[1:])
+        structs[m.group(2)] = type(camel, (C.Structure,), {"_fields_": fields, "__doc__": m.group(2)})
+        return " "
+    text = re.sub(r"typedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(gank_\w+)\s*;", struct, text)
+    prototypes, returns = {}, {}
+    *decls, tail = text.split(";")
+    if tail.strip() not in ("", "}"):           # (`}` closes extern "C")
+        raise bad(tail, "declaration without `;`")
+    for decl in filter(None, (d.strip() for d in decls)):
+        m = re.fullmatch(r"([\w\s*]+?)\s*\b(gank_[a-z0-9_]+)\s*\(([^()]*)\)", decl)
+        ret = re.sub(r"\s*\*", "*", " ".join(m.group(1).split())) if m else None
+        if ret not in _RETURNS or m.group(2) in prototypes:
+            raise bad(decl, "not one new declaration `ret gank_name(args);` with ret one of " + ", ".join(_RETURNS))
+        args = [] if m.group(3).strip() in ("", "void") else m.group(3).split(",")
+        prototypes[m.group(2)], returns[m.group(2)] = [_ctype(a, m.group(2), structs)[1] for a in args], _RETURNS[ret]
+    if len(prototypes) != expected:
+        raise RuntimeError(f"gank.h: {expected} `gank_name(` tokens but {len(prototypes)} declarations read")
+    return defines, structs, prototypes, returns
 
 
-class PrepDesc(C.Structure):
-    """gank_prep_desc"""
-    _fields_ = [("w", P), ("wf", P), ("wd", P), ("ksize", I), ("Cin", I), ("Cout", I), ("kind", I), ("cin_pitch", I)]
-
-
-class Res8Head(C.Structure):
-    """gank_res8_head"""
-    _fields_ = [("logits", P), ("head_w", P), ("pooled", P), ("loss", P), ("w_grad", P), ("b_grad", P), ("n_real", I), ("mode", I),
-                ("loss_scale", F)]
-
-
-class LabelDenseDesc(C.Structure):
-    """gank_label_dense_desc"""
-    _fields_ = [("table", P), ("bias", P), ("out", P), ("V", I), ("D", I), ("weight", I)]
-
-
-class CriticFeedDesc(C.Structure):
-    """gank_critic_feed_desc"""
-    _fields_ = [("real_all", P), ("labels_all", P), ("fake_all", P), ("both", P), ("labels2", P), ("slot", P), ("rng_state", P),
-                ("done_counter", P), ("B", I), ("n_slots", I)]
-
-
-# name -> argument ctypes (all return int unless listed in _RET)
-PROTOTYPES = {
-    "gank_version": [],
-    "gank_act_dtype": [],
-    "gank_last_error": [],
-    "gank_conv2d_prep_weights": [P, P, P, I, I, I, P],
-    "gank_conv2d_prep_weights_batched": [C.POINTER(PrepDesc), I, P],
-    "gank_conv2d_fprop": [P, P, P, P, P, P, I, I, I, I, I, I, I, F, P],
-    "gank_conv2d_fprop_stats": [P, P, P, P, P, P, I, I, I, I, I, I, I, F, P, I, P, P],
-    "gank_conv2d_dgrad": [P, P, P, P, P, I, I, I, I, I, I, I, F, P],
-    "gank_meanpool_conv1x1_fprop": [P, P, P, P, P, I, I, I, I, I, P],
-    "gank_image_conv_pair_fprop": [P, P, P, P, P, P, P, P, I, I, I, I, I, P],
-    "gank_conv2d_wgrad_batched": [C.POINTER(WgradItem), I, I, I, I, I, I, I, I, F, P],
-    "gank_conv2d_wgrad_narrow_pair": [P, P, P, P, I, I, I, I, I, P, P, P, P, I, I, I, I, I, F, P],
-    "gank_conv2d_wgrad_ws_elems": [I, I, I, I, I, I, I],
-    "gank_conv1x1_wgrad_dgrad": [P, P, P, P, P, I, P, I, I, I, I, I, P],
-    "gank_conv2d_wgrad": [P, P, P, P, P, L, I, I, I, I, I, I, I, F, P],
-    "gank_upconv3x3_prep_weights": [P, P, P, I, I, P],
-    "gank_upconv3x3_fprop": [P, P, P, P, P, I, I, I, I, I, I, P],
-    "gank_upconv3x3_fprop_stats": [P, P, P, P, P, I, I, I, I, I, I, P, I, P, P],
-    "gank_upconv3x3_dgrad": [P, P, P, P, I, I, I, I, I, P],
-    "gank_convpool3x3_prep_weights": [P, P, P, I, I, P],
-    "gank_convpool3x3_fprop": [P, P, P, P, P, I, I, I, I, I, I, P],
-    "gank_convpool3x3_dgrad": [P, P, P, P, I, I, I, I, I, P],
-    "gank_convpool3x3_wgrad": [P, P, P, P, P, L, I, I, I, I, I, I, P],
-    "gank_convpool3x3_wgrad_ws_elems": [I, I, I, I, I],
-    "gank_upconv3x3_wgrad_ws_elems": [I, I, I, I, I],
-    "gank_upconv3x3_wgrad": [P, P, P, P, L, I, I, I, I, I, P],
-    "gank_conv2d_general_fprop": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
-    "gank_conv2d_general_dgrad": [P, P, P, P, I, I, I, I, I, I, I, I, I, P],
-    "gank_conv2d_general_wgrad": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
-    "gank_res8_chain_fwd": [P, P, P, P, P, P, I, I, I, P],
-    "gank_res8_chain_bwd": [P, P, P, P, P, P, P, P, P, I, I, I, P],
-    "gank_phase_stack4": [P, P, I, I, I, P],
-    "gank_pad_rows": [P, P, C.c_long, I, I, I, I, P],
-    "gank_tile_rows": [P, P, I, I, I, P],
-    "gank_fewout_pack": [P, P, I, I, I, I, I, P],
-    "gank_zero_f32": [P, C.c_long, P],
-    "gank_img16_conv3x3": [P, P, P, P, P, P, I, I, I, I, P],
-    "gank_cbn_relu_img16_conv3x3": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, I, P],
-    "gank_img16_conv3x3_stats": [P, P, P, P, P, P, I, I, I, I, P, I, P],
-    "gank_res8_chain_fwd_head": [P, P, P, P, P, P, P, P, P, I, I, I, P],
-    "gank_res8_chain_bwd_head": [C.POINTER(Res8Head), P, P, P, P, P, P, P, I, I, I, P],
-    "gank_res8_conv3x3": [P, P, P, P, P, I, I, I, I, P, I, P],
-    "gank_im2col_narrow": [P, P, I, I, I, I, I, I, I, I, I, I, P],
-    "gank_tap_gather_up2": [P, P, P, I, I, I, I, I, I, I, I, P],
-    "gank_tap_scatter_up2": [P, P, I, I, I, I, I, I, I, P],
-    "gank_depth_to_space2": [P, P, I, I, I, I, P],
-    "gank_space_to_depth2": [P, P, I, I, I, I, P],
-    "gank_cpool_res_fprop": [P, P, P, P, P, I, I, I, I, I, I, P],
-    "gank_cpool_res_dgrad": [P, P, P, P, I, I, I, I, I, P],
-    "gank_cpool_res_dgrad_image_wgrad": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, P],
-    "gank_sum_slabs": [C.POINTER(SlabJob), I, P],
-    "gank_convpool3x3_wgrad_job": [P, P, P, P, P, L, I, I, I, I, I, I, C.POINTER(SlabJob), P],
-    "gank_conv2d_wgrad_slab_elems": [I, I, I, I, I, I, I],
-    "gank_conv2d_wgrad_slabs": [P, P, P, P, I, I, I, I, I, I, I, F, P, L, C.POINTER(SlabJob), P],
-    "gank_conv2d_wgrad_slab_splits": [I, I, I, I, I, I, I],
-    "gank_conv2d_wgrad_slabs_rows": [P, P, P, P, I, I, I, I, I, I, I, I, F, P, L, C.POINTER(SlabJob), P],
-    "gank_conv2d_wgrad_slabs_rows_tap_sums": [P, P, P, P, I, I, I, I, I, I, I, I, F, P, L, C.POINTER(SlabJob), P, I, P, P],
-    "gank_conv2d_wgrad_batched_ws_elems": [I, I, I, I, I, I, I, I],
-    "gank_conv2d_wgrad_batched_slabs": [C.POINTER(WgradItem), I, I, I, I, I, I, I, I, F, P, L, C.POINTER(SlabJob), P],
-    "gank_deconv2d_prep_phases": [P, P, I, I, I, P],
-    "gank_deconv2d_fprop": [P, P, P, P, I, I, I, I, I, I, P],
-    "gank_deconv2d_dgrad": [P, P, P, I, I, I, I, I, I, P],
-    "gank_deconv2d_wgrad": [P, P, P, I, I, I, I, I, I, P],
-    "gank_colsum_bf16": [P, P, L, I, F, P],
-    "gank_sn_ws_floats": [I, I],
-    "gank_sn_power_iter_fwd": [C.POINTER(SnDesc), I, P],
-    "gank_sn_power_iter_bwd": [C.POINTER(SnDesc), I, P],
-    "gank_sn_power_iter_fwd_prep": [C.POINTER(SnDesc), I, C.POINTER(PrepDesc), C.POINTER(C.c_int), I, C.POINTER(LabelDenseDesc), P],
-    "gank_sn_power_iter_fwd_a": [C.POINTER(SnDesc), I, P],
-    "gank_sn_power_iter_fwd_b_prep": [C.POINTER(SnDesc), I, C.POINTER(PrepDesc), C.POINTER(C.c_int), I, C.POINTER(LabelDenseDesc), P, P, P, I, P],
-    "gank_sn_power_iter_fwd_b_prep_feed": [C.POINTER(SnDesc), I, C.POINTER(PrepDesc), C.POINTER(C.c_int), I, C.POINTER(LabelDenseDesc), P, P, P, I,
-                                           C.POINTER(CriticFeedDesc), P],
-    "gank_sn_power_iter_bwd_gw": [C.POINTER(SnDesc), I, P],
-    "gank_sn_adam_fwd_a": [C.POINTER(SnDesc), I, C.POINTER(C.c_void_p), P, P, P, P, L, P, P, P, P, I, P, P, P],
-    "gank_label_dense_table": [P, P, P, P, P, I, I, I, P],
-    "gank_concat_label_fwd": [P, P, P, P, I, I, I, I, I, P],
-    "gank_concat_label_bwd": [P, P, P, I, I, I, I, P],
-    "gank_label_dense_bwd": [P, P, P, P, P, P, P, I, I, I, I, P],
-    "gank_label_conv3x3_bwd_pooled": [P, P, P, I, P, I, I, I, I, I, P, P, P, P, I, I, I, P],
-    "gank_label_dense_bwd_parts": [P, I, P, P, P, P, P, I, I, I, P],
-    "gank_sum_slabs_label_bwd": [P, I, P, P, P, I, P, I, I, I, I, I, P, P, P, I, I, I, P],
-    "gank_concat_label_pool_fwd": [P, P, P, P, P, I, I, I, I, I, I, P],
-    "gank_concat_label_unpool_bwd": [P, P, P, P, I, I, I, I, I, P],
-    "gank_concat_label_unpool_bwd_factored": [P, P, P, P, P, I, P, P, I, I, I, I, I, I, P],
-    "gank_label_conv3x3_table": [P, I, I, I, I, P, I, P, P, P, I, P, P],
-    "gank_label_conv3x3_table_pooled": [P, I, I, I, I, P, I, P, P, P, I, P, P, P, I, I, I, P],
-    "gank_label_conv3x3_table_pooled_shortcut": [P, I, I, I, I, P, I, P, P, P, I, P, P, P, I, I, I, P, I, P, I, P, P],
-    "gank_img16_conv3x3_label_bias": [P, P, P, P, I, P, I, I, I, I, P],
-    "gank_img16_conv3x3_dgrad_unpool": [P, P, P, P, I, F, P, I, I, I, P],
-    "gank_img16_conv3x3_label_bwd": [P, P, P, P, I, I, I, I, P, P, I, P, I, I, I, I, P, P, P],
-    "gank_label_conv3x3_bwd_ws_floats": [I, I],
-    "gank_label_conv3x3_bwd": [P, P, P, I, P, I, I, I, I, I, I, I, P, P, P, P, P],
-    "gank_cbn_parts": [L],
-    "gank_cbn_fwd": [P, P, P, P, P, P, P, I, I, I, I, I, I, P],
-    "gank_cbn_fwd_from_sums": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P],
-    "gank_cbn_fwd_eps": [P, P, P, P, P, P, P, I, I, I, I, I, I, F, P],
-    "gank_layer_norm_fwd": [P, P, P, P, P, I, I, I, F, P],
-    "gank_layer_norm_bwd": [P, P, P, P, P, P, P, I, I, I, P],
-    "gank_pixel_norm_fwd": [P, P, L, I, F, P],
-    "gank_pixel_norm_bwd": [P, P, P, L, I, F, P],
-    "gank_cbn_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
-    "gank_cbn_stats": [P, P, P, I, I, I, I, F, P],
-    "gank_cbn_stats_from_sums": [P, P, P, I, I, L, F, P],
-    "gank_cbn_relu_conv3x3_fprop": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P],
-    "gank_cbn_bwd_remask": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
-    "gank_cbn_bwd_ws_floats": [I, I, I, I],
-    "gank_cbn_bwd_ws": [P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, P],
-    "gank_pool2x2": [P, P, P, I, I, I, I, F, P],
-    "gank_unpool2x2_add": [P, P, P, I, I, I, I, F, P],
-    "gank_add_bf16": [P, P, P, L, P],
-    "gank_relu_fwd": [P, P, L, F, P],
-    "gank_relu_bwd": [P, P, P, L, F, P],
-    "gank_tanh_bwd": [P, P, P, L, P],
-    "gank_scale_f32": [P, P, P, L, P],
-    "gank_weighted_sum4_f32": [P, P, P, P, F, F, F, F, P, L, P],
-    "gank_linear_fwd": [P, P, P, P, I, I, I, P],
-    "gank_linear_fwd_f32out": [P, P, P, P, I, I, I, P],
-    "gank_linear_bwd": [P, P, P, P, P, P, I, I, I, P],
-    "gank_copy_bytes": [P, P, L, P],
-    "gank_copy_bytes_gather": [P, P, I, L, P],
-    "gank_copy_bytes_gather2": [P, P, I, L, P, P, I, L, P],
-    "gank_cast_f32_bf16": [P, P, L, P],
-    "gank_cast_bf16_f32": [P, P, L, P],
-    "gank_relu_meanpool_hw_fwd": [P, P, I, I, I, P],
-    "gank_relu_meanpool_hw_bwd": [P, P, P, I, I, I, P],
-    "gank_concat_tile_fwd": [P, P, P, I, I, I, I, P],
-    "gank_concat_tile_bwd": [P, P, P, I, I, I, I, P],
-    "gank_embedding_fwd": [P, P, P, I, I, I, P],
-    "gank_embedding_bwd": [P, P, P, I, I, I, P],
-    "gank_critic_head_hinge": [P, P, P, P, P, P, P, P, I, I, I, I, P],
-    "gank_critic_head_hinge_scaled": [P, P, P, P, P, P, P, P, I, I, I, I, F, P],
-    "gank_proj_head_fwd": [P, P, P, P, P, P, I, I, I, P],
-    "gank_proj_head_bwd": [P, P, P, P, P, P, P, P, P, I, I, I, P],
-    "gank_proj_head_hinge_scaled": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, P],
-    "gank_hinge_d_loss": [P, P, P, P, I, I, P],
-    "gank_gan_pointwise_loss": [P, P, P, P, I, I, I, P],
-    "gank_hinge_g_loss": [P, P, P, P, I, P],
-    "gank_wgan_d_loss": [P, P, P, P, I, I, P],
-    "gank_softmax_xent": [P, P, P, P, P, I, I, P],
-    "gank_loss_grad_scale": [P, P, P, L, P],
-    "gank_bn_bwd_bwd": [P, P, P, P, P, P, P, P, P, L, I, P],
-    "gank_bn_moving_update": [P, P, P, P, P, I, I, L, F, F, P],
-    "gank_gp_loss": [P, P, P, P, I, L, F, P],
-    "gank_lerp_rows": [P, P, P, P, I, L, P],
-    "gank_sum_hw": [P, P, I, I, I, F, P],
-    "gank_bcast_hw": [P, P, I, I, I, F, P],
-    "gank_rng_uniform_f32": [P, L, P, P],
-    "gank_axpby_bf16": [P, P, F, F, P, L, P],
-    "gank_blend_dev": [P, P, P, P, L, I, P],
-    "gank_minibatch_std_fwd": [P, P, P, I, I, I, P],
-    "gank_minibatch_std_bwd": [P, P, P, P, I, I, I, P],
-    "gank_resize_bilinear": [P, P, I, I, I, I, I, I, P],
-    "gank_resize_nearest_fwd": [P, P, I, I, I, I, I, I, P],
-    "gank_resize_nearest_bwd": [P, P, I, I, I, I, I, I, P],
-    "gank_concat_channels": [P, P, P, L, I, I, P],
-    "gank_pool2d": [P, P, I, I, I, I, I, I, I, I, I, I, I, I, P],
-    "gank_relu_to_channels": [P, P, L, I, I, I, P],
-    "gank_split_channels": [P, P, P, L, I, I, P],
-    "gank_l1_loss": [P, P, P, P, P, L, P],
-    "gank_dropout_fwd": [P, P, P, L, F, P, P],
-    "gank_dropout_bwd": [P, P, P, L, F, P],
-    "gank_adam_tf": [P, P, P, P, P, P, P, L, L, P],
-    "gank_adam_tf_health": [P, P, P, P, P, P, P, L, L, P, P],
-    "gank_counter_add": [P, C.c_int64, P],
-    "gank_preprocess_real": [P, P, P, I, P],
-    "gank_rng_normal_bf16": [P, L, P, P],
-    "gank_generator_feed": [P, L, I, P, L, P, L, P, P],
-    "gank_rng_labels": [P, L, I, P, P],
-    "gank_prof_enable": [I],
-    "gank_prof_reset": [],
-    "gank_prof_collect": [I, C.POINTER(C.c_double), C.POINTER(C.c_double)],
-    "gank_prof_calibrate": [I, P],
-    "gank_prof_bytes": [I],
-    "gank_prof_kernel_stats": [I, I, C.c_char_p, I, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
-    "gank_critic_feed": [P, P, P, P, P, P, P, P, I, I, P],
-    "gank_debug_tr_probe": [P, P],
-    "gank_msssim_level": [P, P, I, I, I, I, I, I, C.POINTER(C.c_float), F, F, F, P, P, P, P],
-    "gank_msssim_level_parts": [I, I, I, I],
-    "gank_mean_hw_f32": [P, P, I, I, I, P],
-    "gank_moments_update": [P, I, I, I, P, P, P],
-    "gank_inception_score_update": [P, I, I, C.c_longlong, C.c_longlong, I, P, P, P],
-    "gank_kid_block_sums": [P, I, P, I, I, P, P, I, I, C.c_double, C.c_double, I, P, P],
-    "gank_kid_finish": [P, I, I, P, P],
-    "gank_prd_knn_partial": [P, I, I, I, I, P, P],
-    "gank_prd_knn_finish": [P, I, I, I, P, P],
-    "gank_prd_counts_partial": [P, I, P, I, I, P, I, P, P, P],
-    "gank_prd_counts_finish": [P, P, I, I, P, P, P],
-    "gank_swd_pyr_down": [P, I, I, I, I, P, P],
-    "gank_swd_laplacian": [P, P, I, I, I, I, P],
-    "gank_swd_patch_stats_parts": [I],
-    "gank_swd_patch_stats": [P, I, I, I, I, P, P, I, I, I, P, P, P, P],
-    "gank_swd_project": [P, I, I, I, I, P, P, I, I, I, P, P, I, P, P],
-    "gank_swd_sort_max_rows": [],
-    "gank_swd_sort_ws_elems": [I, I],
-    "gank_swd_sort_rows": [P, P, I, I, P, P],
-    "gank_swd_sorted_l1_parts": [I],
-    "gank_swd_sorted_l1": [P, P, I, I, P, P],
-    "gank_pix2pix_load_examples": [P, I, I, I, I, I, I, I, I, P, P, P, I, P],
-    "gank_rgb_to_lab": [P, P, L, P],
-    "gank_lab_to_rgb": [P, P, L, P],
-    "gank_pix2pix_convert_u8": [P, P, I, L, I, I, I, I, P, P],
-}
-_RET = {"gank_last_error": C.c_char_p, "gank_sn_ws_floats": C.c_long, "gank_cbn_bwd_ws_floats": C.c_long, "gank_label_conv3x3_bwd_ws_floats": C.c_long, "gank_conv2d_wgrad_ws_elems": C.c_long, "gank_convpool3x3_wgrad_ws_elems": C.c_long, "gank_upconv3x3_wgrad_ws_elems": C.c_long, "gank_conv2d_wgrad_batched_ws_elems": C.c_long, "gank_conv2d_wgrad_slab_elems": C.c_long, "gank_swd_sort_ws_elems": C.c_long, "gank_prof_calibrate": C.c_double, "gank_prof_bytes": C.c_double}
+with open(HEADER) as _f:
+    DEFINES, STRUCTS, PROTOTYPES, RESTYPES = parse_header(_f.read())     # PROTOTYPES: symbol -> argument ctypes
+# Published under the names the callers import: the constants without their prefix (GANK_IN_RELU -> IN_RELU, GANK_STAT_SLOTS ->
+# STAT_SLOTS, ...) and each descriptor class under the CamelCase of its C name without it (gank_sn_desc -> SnDesc, ...).
+globals().update({k[len("GANK_"):]: v for k, v in DEFINES.items()})
+globals().update({s.__name__: s for s in STRUCTS.values()})
 
 _lib = None
 
@@ -289,7 +121,9 @@ def load():
         except AttributeError as e:
             raise RuntimeError(f"libgank.so does not export {name}; rebuild it") from e
         fn.argtypes = args
-        fn.restype = _RET.get(name, C.c_int)
+        fn.restype = RESTYPES[name]
+    if lib.gank_version() != DEFINES["GANK_VERSION"]:
+        raise RuntimeError(f"{LIB_PATH} is version {lib.gank_version()}, include/gank.h declares {DEFINES['GANK_VERSION']}; rebuild it")
     if lib.gank_act_dtype() != (1 if DTYPE == "fp16" else 0):
         raise RuntimeError(f"{LIB_PATH} was built for {'fp16' if lib.gank_act_dtype() else 'bf16'} buffers, this process runs GANK_DTYPE={DTYPE}")
     _lib = lib

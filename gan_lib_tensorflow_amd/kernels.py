@@ -1,6 +1,8 @@
 """Tensor-level wrappers over the C ABI (include/gank.h).  torch is used for device memory and
 streams only: every function checks its operands, then enqueues HIP kernels from libgank.so on the
-current torch stream.  Nothing here has a CPU path."""
+current torch stream.  Nothing here has a CPU path.  The argument types, the descriptor structs and the
+flag constants used below are the ones _lib derives from the header; a wrapper for a new entry point
+needs its declaration there and nothing else."""
 import ctypes as C
 
 import torch
