@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INC = os.path.join(os.path.dirname(HERE), "include")
-LIB = os.path.join(HERE, os.environ.get("GANK_LIB_NAME", "libgank.so"))   # experiment builds: GANK_LIB_NAME + GANK_EXTRA_FLAGS
+LIB = os.path.join(HERE, os.environ.get("GANK_LIB_NAME", "libgank.so"))   # a second library beside the product: GANK_LIB_NAME + GANK_EXTRA_FLAGS
 SOURCES = ["api.hip", "conv_igemm.hip", "conv_wgrad.hip", "conv_resident.hip", "label_conv.hip", "acgan_ops.hip", "pggan_pix_ops.hip", "elementwise.hip", "sn.hip", "cbn.hip", "loss_opt.hip", "proj_head.hip", "linear.hip", "norms.hip", "msssim.hip", "pix_input.hip", "fid.hip", "inception_score.hip", "kid.hip", "prd.hip", "swd.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"] + \
     os.environ.get("GANK_EXTRA_FLAGS", "").split()
@@ -31,8 +31,8 @@ def build(force=False, verbose=True, variants=("bf16", "fp16")):
     for variant in variants:
         if variant == "fp16":
             if "GANK_LIB_NAME" in os.environ or os.environ.get("GANK_EXTRA_FLAGS"):
-                continue        # an experiment build (scratch/README.md) is the bf16 library under its own name: the production
-                                # fp16 objects must not be rebuilt with the experiment's flags
+                continue        # a build with extra flags is the bf16 library under its own name: the production
+                                # fp16 objects must not be rebuilt with those flags
             lib, flags, objdir = os.path.join(HERE, "libgank_f16.so"), base_flags + ["-DGANK_ACT_F16"], "_obj_f16"
         else:
             lib, flags = os.path.join(HERE, os.environ.get("GANK_LIB_NAME", "libgank.so")), base_flags

@@ -331,8 +331,7 @@ __global__ __launch_bounds__(512) void cbn_fwd_small_kernel(const bf16* __restri
   }
 }
 static bool cbn_fwd_small_ok(const CbnGeom& q) {
-  static const int env = gank_tune("GANK_CBN_SMALL", 1);   // experiment knob: 0 keeps the three-launch form for small towers
-  return env && q.rows_per_group <= CFS_LANES * CFS_ROWS && q.C % 64 == 0;
+  return q.rows_per_group <= CFS_LANES * CFS_ROWS && q.C % 64 == 0;
 }
 
 extern "C" int gank_cbn_fwd_eps(const void* x, const int32_t* labels, const float* gamma, const float* beta, void* y,

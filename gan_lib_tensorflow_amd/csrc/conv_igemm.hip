@@ -15,23 +15,9 @@
 // Replaces tf.nn.conv2d / Conv2DBackpropInput at common/ops/conv2d.py:180-187 and the
 // surrounding block-library glue (SNGAN/gan_cifar_resnet.py:112-153,186,198,209,261).
 #include "gank_common.h"
-#ifdef GANK_TUNING
-// timing-only experiment (GANK_STATS_DBG=1): the statistics epilogues skip their atomics (set once per process, before the first launch)
-static __device__ int gank_stats_dbg = 0;
-static void gank_stats_dbg_init() {
-  static const int v = gank_tune("GANK_STATS_DBG", 0);
-  static bool done = false;
-  if (!done) { done = true; if (v) (void)hipMemcpyToSymbol(HIP_SYMBOL(gank_stats_dbg), &v, sizeof(int)); }
-}
-#else
-static inline void gank_stats_dbg_init() {}
-#endif
 #include <stdlib.h>
 #include <type_traits>
 
-#ifndef GANK_KMODE
-#define GANK_KMODE 0
-#endif
 #define IG_IN_ZEROINS2X 16
 #define IG_IN_STRIDE2 32
 #define IG_RES_UP2X 128       // residual is [N,H/2,W/2,Cout]: read at (oh>>1, ow>>1) (public GANK_RES_UPSAMPLE2X)
@@ -69,11 +55,6 @@ struct IgemmArgs {
   int cbn_n_per_group, cbn_n_labels;
   bf16* aux_out;             // narrow-input kernel, POOL: the 2x2 mean-pooled input it gathered, [N,H,W,CIN] (or null)
 };
-
-static int phase_inner_env() {
-  static const int v = gank_tune("GANK_PHASE_INNER", 1);   // experiment knob: GANK_PHASE_INNER=0 restores the phase-slowest block order
-  return v;
-}
 
 constexpr int LROW = 72;  // LDS row length in bf16 (64 + 8 pad) = 144 B
 
@@ -235,8 +216,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(IgemmArgs a) {
   // After the last step it stays put, so the PF-1 trailing refills of the ring re-load the last step.
   const int last = a.nsteps - 1;
   int cur = 0, cur_c0 = 0, cur_tap = 0, cur_dh = -pad_h, cur_dw = -pad_w;
-  constexpr bool TAP_INNER = (GANK_KMODE & 1) != 0;   // compile-time experiment knob (build.py GANK_KMODE)
-  constexpr int W_AUX = (GANK_KMODE >> 1) == 1 ? 2 : ((GANK_KMODE >> 1) == 2 ? 16 : 0);   // nt / sc1 / default
 
   auto load_next = [&](u32x4 (&rP)[CP], u32x4 (&rW)[CW]) {
     if constexpr (!PACKED) {
@@ -289,23 +268,15 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(IgemmArgs a) {
       }
     }
     if constexpr (!PACKED) {
-      // weights bypass the CU's 32 KB L1 (nt): they are streamed once per block, while the activation patch of
-      // a 64-channel chunk is re-read by all taps of that chunk (tap-inner order below) and should stay in L1
       const int wk = (cur_tap * a.Cin + cur_c0) * 2;
 #pragma unroll
-      for (int j = 0; j < CW; j++) rW[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, w_off[j], wk, W_AUX);
+      for (int j = 0; j < CW; j++) rW[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, w_off[j], wk, 0);
       if (cur < last) {
         cur++;
-        if constexpr (TAP_INNER) {  // K order: channel chunk outer, tap inner
-          cur_tap++;
+        cur_c0 += 64;               // K order: tap outer, channel chunk inner
+        if (cur_c0 >= a.Cin) {
+          cur_c0 = 0; cur_tap++;
           if (++cur_dw > a.ks - 1 - pad_w) { cur_dw = -pad_w; cur_dh++; }
-          if (cur_tap >= a.taps) { cur_tap = 0; cur_dh = -pad_h; cur_dw = -pad_w; cur_c0 += 64; }
-        } else {                    // K order: tap outer, channel chunk inner
-          cur_c0 += 64;
-          if (cur_c0 >= a.Cin) {
-            cur_c0 = 0; cur_tap++;
-            if (++cur_dw > a.ks - 1 - pad_w) { cur_dw = -pad_w; cur_dh++; }
-          }
         }
       }
     } else {
@@ -495,9 +466,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(IgemmArgs a) {
       const int n0 = a.shw >= 0 ? (m0 >> a.shw) : m0 / (a.H * a.W);
       float* dst = a.stat_sums + ((long)(n0 / a.stat_n_per_group) * GANK_STAT_SLOTS + (blockIdx.x % GANK_STAT_SLOTS)) * 2 * a.Cout;
       const int co = tile_n * BN + (wave_n * TN + (r >> 4)) * 32 + 16 * ((r >> 3) & 1) + 8 * h + (r & 7);
-#ifdef GANK_TUNING
-      if (gank_stats_dbg) return;
-#endif
       atomicAdd(dst + co, keep1);
       atomicAdd(dst + a.Cout + co, keep2);
     }
@@ -941,10 +909,9 @@ static int launch_few(const IgemmArgs& a0, hipStream_t s) {
   return 0;
 }
 static bool few_ok(const IgemmArgs& a) {
-  static const int env = gank_tune("GANK_IGEMM_FEW", 1);   // experiment knob: 0 keeps the 32-row patch kernel
-  // (channel-inner K order only: the kernel walks [tap][channel]; it accumulates no statistics -- `tl_stats_done` stays 0 and the
-  //  caller's batch-norm pass computes them, as after the 32-row patch kernel it replaces)
-  return env && a.korder == 0 && a.Cout <= 3 && a.CoutPad == 32 && a.Cin % 64 == 0 && a.Kpad == 9 * a.Cin && !(a.flags & IG_RES_UP2X) &&
+  // (it accumulates no statistics -- `tl_stats_done` stays 0 and the caller's batch-norm pass computes them, as after the
+  //  32-row patch kernel it replaces)
+  return a.Cout <= 3 && a.CoutPad == 32 && a.Cin % 64 == 0 && a.Kpad == 9 * a.Cin && !(a.flags & IG_RES_UP2X) &&
          (size_t)(10 * HROWP + 4 * (a.Kpad + 8)) * sizeof(bf16) <= 160 * 1024;
 }
 
@@ -952,7 +919,7 @@ template <int MODE>    // MODE has bit 2 set
 static int launch_patch_phase(const IgemmArgs& a0, hipStream_t s) {
   IgemmArgs a = a0;
   a.tiles_pp = a.N * (a.H / 8) * (a.W / 16);
-  a.phase_inner = phase_inner_env();
+  a.phase_inner = 1;
   a.tiles_m = 4 * a.tiles_pp;
   a.tiles_n = a.CoutPad / 128;
   const size_t lds = ((size_t)10 * HROWP + (size_t)2 * 128 * LROW) * sizeof(bf16);
@@ -965,8 +932,7 @@ static int launch_patch_phase(const IgemmArgs& a0, hipStream_t s) {
   return 0;
 }
 static bool patch_phase_ok(const IgemmArgs& a) {   // a.H, a.W = low-res grid; a.Cin % 64 == 0 is checked by the callers
-  static const int env = gank_tune("GANK_IGEMM_PATCH_PHASE", 1);   // GANK_IGEMM_PATCH_PHASE=0 keeps the per-tap phase kernel
-  return env && a.W % 16 == 0 && a.H % 8 == 0 && a.CoutPad % 128 == 0 && a.Cout % 4 == 0 && a.Cin % 64 == 0;
+  return a.W % 16 == 0 && a.H % 8 == 0 && a.CoutPad % 128 == 0 && a.Cout % 4 == 0 && a.Cin % 64 == 0;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1159,9 +1125,9 @@ static int launch_narrow_in(const IgemmArgs& a0, hipStream_t s) {
 // Every kernel above sits at ~0.9 PFLOP/s: a 128-wide tile, 2-3 blocks per CU, one __syncthreads (with its vmcnt(0)
 // drain) per K-step.  This one has the structure that gets past that on a GEMM:
 //   * one 512-thread block per CU owns 256 pixels x 256 couts; wave (wm, wn) = 128 pixels x 64 couts = 8 x 4 tiles of
-//     v_mfma_f32_16x16x32 (GANK_PP_M16, default; 4 x 2 of 32x32x16 otherwise), 128 accumulator registers, 12 fragment reads
+//     v_mfma_f32_16x16x32, 128 accumulator registers, 12 fragment reads
 //     (ds_read_b128) per K-step;
-//   * a phase is one K-step of 32 channels of one tap: {12 fragment reads R, LDS-DMA issues, counted vmcnt, 32 (16) MFMAs M}
+//   * a phase is one K-step of 32 channels of one tap: {12 fragment reads R, LDS-DMA issues, counted vmcnt, 32 MFMAs M}
 //     with ONE s_barrier, which group 0 (waves 0-3) takes between R and M and group 1 (waves 4-7: the other wave of
 //     each SIMD) at the top of the phase.  After barrier p group 0 therefore runs {M_p, R_p+1} while group 1 runs
 //     {R_p, M_p}: each SIMD's matrix pipe has one group's MFMAs beside the other group's reads and staging;
@@ -1199,13 +1165,10 @@ __device__ __forceinline__ void pp_wait_vmcnt() {
   if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
 }
 
-// Matrix instruction of the two-group kernel.  1 (default): v_mfma_f32_16x16x32 -- the same multiply-adds in twice as many
-// instructions of half the size, the same 12 fragment reads per K-step.  On this power-bound kernel it runs 6-10 % faster than
-// the 32x32x16 form (timing experiment at equal memory traffic: 145 -> 130 us at n = 128, 312 -> 288 us at n = 320; the guide
-// reports 1.12-1.15x for bare loops).  0: the 32x32x16 form (kept for A/B runs: -DGANK_PP_M16=0).
-#ifndef GANK_PP_M16
-#define GANK_PP_M16 1
-#endif
+// Matrix instruction of the two-group kernel: v_mfma_f32_16x16x32 -- the same multiply-adds as the 32x32x16 form in twice as
+// many instructions of half the size, the same 12 fragment reads per K-step.  On this power-bound kernel it runs 6-10 % faster
+// (timing experiment at equal memory traffic: 145 -> 130 us at n = 128, 312 -> 288 us at n = 320; the guide reports 1.12-1.15x
+// for bare loops).
 #ifdef GANK_ACT_F16
 #define GANK_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
 #else
@@ -1218,22 +1181,11 @@ __global__ __launch_bounds__(512) void conv_igemm_pp_kernel(IgemmArgs a) {
   constexpr int PHH = 256 / PW;                      // patch rows
   constexpr int HW_ = PW + 2, HROW = HW_ * 64;       // halo width (pixels), halo row pitch (bytes)
   constexpr int HPX = (PHH + 2) * HW_;               // halo pixels
-  constexpr int RS = 32 / PW;                        // patch rows per 32-pixel MFMA tile
-  // halo swizzle: 16-byte chunk c of halo pixel (hy, hx) sits in slot c ^ ((hx >> HSW) & 3).  ds_read_b128 is served in four
-  // fixed 16-lane groups ({0-3,12-15,20-27}, ...); with the 18-pixel rows of PW = 16 (pitch = 8 slots mod 16) a group mixes
-  // two patch rows and (hx >> 2) left two lanes of most groups on one slot: 6.7 LDS cycles per read instead of 4 by the bank
-  // rule, SQ_LDS_BANK_CONFLICT = 30 % of SQ_LDS_IDX_ACTIVE.  (hx >> 1) is conflict-free there, (hx >> 2) for one-row tiles.
-  constexpr int HSW = PW == 16 ? 1 : 2;
-#if GANK_PP_M16
-  // 16x16x32 fragments: lane l reads 16-byte chunk l >> 4 of row l & 15 (a cout, or a pixel of one 16-pixel run of a patch
+  // halo swizzle, 16x16x32 fragments: lane l reads 16-byte chunk l >> 4 of row l & 15 (a cout, or a pixel of one 16-pixel run of a patch
   // row: no two-row tiles here).  chunk ^ ((row >> 1) & 2) puts the 16 lanes of every ds_read_b128 lane group on 16 different
   // slots for every start column of the run (brute force over the four groups and all shifts 0..18), weights included.
   auto pp_hswz = [](int hx) { return (hx >> 1) & 2; };
   auto pp_wswz = [](int co) { return (co >> 1) & 2; };
-#else
-  auto pp_hswz = [](int hx) { return (hx >> HSW) & 3; };
-  auto pp_wswz = [](int co) { return (co >> 2) & 3; };
-#endif
   static_assert(PW == 32 || PW == 16, "patch width");
   static_assert(HPX * 64 <= PP_HALO_BYTES, "halo image");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1241,8 +1193,6 @@ __global__ __launch_bounds__(512) void conv_igemm_pp_kernel(IgemmArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
-  const int r = lane & 31, h = lane >> 5;
-  const int prow = RS == 1 ? 0 : (r >> 4), pcol = RS == 1 ? r : (r & 15);   // this lane's pixel inside a tile
 
   const int nwg = a.tiles_m * a.tiles_n;
   const int lid = xcd_remap(blockIdx.x, nwg);
@@ -1288,7 +1238,6 @@ __global__ __launch_bounds__(512) void conv_igemm_pp_kernel(IgemmArgs a) {
   // fragment read offsets of this lane (bytes): weights row r of the wave's cout range; pixels: halo column pcol + d of
   // the wave's first patch row (+ the tap's row offset as an immediate), d = the tap's column offset 0..2
   constexpr int ND = PHASE ? 2 : 3;
-#if GANK_PP_M16
   const int p16 = lane & 15, kc = lane >> 4;         // row / pixel inside a 16-wide tile, 16-byte K chunk
   constexpr int RPT = PW / 16;                       // 16-pixel tiles per patch row
   int a_lane, b_lane[ND];
@@ -1299,19 +1248,6 @@ __global__ __launch_bounds__(512) void conv_igemm_pp_kernel(IgemmArgs a) {
     const int hy = wm * (PHH / 2) + (PHASE ? 1 - pad_h : 0);
     b_lane[d] = hy * HROW + hx * 64 + ((kc ^ pp_hswz(hx)) << 4);                   // + (j / RPT) * HROW + (j % RPT) * 1024 for pixel tile j
   }
-#else
-  int a_lane[2], b_lane[ND][2];
-#pragma unroll
-  for (int kk = 0; kk < 2; kk++) {
-    a_lane[kk] = PP_WRING + (wn * 64 + r) * 64 + (((kk * 2 + h) ^ pp_wswz(r)) << 4);
-#pragma unroll
-    for (int d = 0; d < ND; d++) {
-      const int hx = pcol + d + (PHASE ? 1 - pad_w : 0);
-      const int hy = wm * (PHH / 2) + prow + (PHASE ? 1 - pad_h : 0);
-      b_lane[d][kk] = hy * HROW + hx * 64 + (((kk * 2 + h) ^ pp_hswz(hx)) << 4);
-    }
-  }
-#endif
 
   const int nch = a.Cin >> 5;
   auto issue_w = [&](int slot_bytes, int c, int tap) {      // K-step (chunk c, tap) -> ring slot
@@ -1326,21 +1262,11 @@ __global__ __launch_bounds__(512) void conv_igemm_pp_kernel(IgemmArgs a) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_t)(smem + buf * PP_HALO_BYTES + (j * 4 + wn) * 1024), 16, (int)(h_off[j] + (unsigned)c * 64u), 0, 0, 0);
   };
 
-#if GANK_PP_M16
   f32x4 acc[4][8];                                   // [cout tile of 16][pixel tile of 16]
 #pragma unroll
   for (int i = 0; i < 4; i++)
 #pragma unroll
     for (int j = 0; j < 8; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#else
-  f32x16 acc[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) acc[i][j][e] = 0.f;
-#endif
 
   // prologue: halo of chunk 0, weights of K-steps 0..3 (issue order matters: the counted waits rely on it)
   if (wm == 1) { issue_h(0, 0, 0); issue_h(0, 0, 3); }
@@ -1367,22 +1293,11 @@ __global__ __launch_bounds__(512) void conv_igemm_pp_kernel(IgemmArgs a) {
       constexpr int t = decltype(tc)::value;
       constexpr int dh1 = PHASE ? t / 2 : t / 3, dw1 = PHASE ? t % 2 : t % 3;
       if (wm == 1) __builtin_amdgcn_s_barrier();
-#if GANK_PP_M16
       bf16x8 fa[4], fb[8];
 #pragma unroll
       for (int i = 0; i < 4; i++) fa[i] = *reinterpret_cast<const bf16x8*>(smem + rslot + i * 1024 + a_lane);
 #pragma unroll
       for (int j = 0; j < 8; j++) fb[j] = *reinterpret_cast<const bf16x8*>(smem + hb + (j / RPT + dh1) * HROW + (j % RPT) * 1024 + b_lane[dw1]);
-#else
-      bf16x8 fa[2][2], fb[4][2];
-#pragma unroll
-      for (int kk = 0; kk < 2; kk++) {
-#pragma unroll
-        for (int i = 0; i < 2; i++) fa[i][kk] = *reinterpret_cast<const bf16x8*>(smem + rslot + i * 2048 + a_lane[kk]);
-#pragma unroll
-        for (int j = 0; j < 4; j++) fb[j][kk] = *reinterpret_cast<const bf16x8*>(smem + hb + (j * RS + dh1) * HROW + b_lane[dw1][kk]);
-      }
-#endif
       // group 1: half of the next chunk's halo, ahead of the weight pieces (clamped past the end: a spare image)
       if constexpr (t < 2) { if (wm == 1) issue_h((c + 1) & 1, cn, 3 * t); }
       {                                                // K-step p + 4 (clamped to the last one: a spare write into a dead slot)
@@ -1395,7 +1310,6 @@ __global__ __launch_bounds__(512) void conv_igemm_pp_kernel(IgemmArgs a) {
       else pp_wait_vmcnt<4>();
       if (wm == 0) __builtin_amdgcn_s_barrier();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if GANK_PP_M16
       if constexpr ((MODE & 1) != 0) {
 #pragma unroll
         for (int j = 0; j < 8; j++) fb[j] = __builtin_bit_cast(bf16x8, relu_bf16x8(__builtin_bit_cast(u32x4, fb[j])));
@@ -1406,22 +1320,6 @@ __global__ __launch_bounds__(512) void conv_igemm_pp_kernel(IgemmArgs a) {
 #pragma unroll
         for (int j = 0; j < 8; j++)
           acc[i][j] = GANK_MFMA16(fa[i], fb[j], acc[i][j]);
-#else
-      if constexpr ((MODE & 1) != 0) {
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-#pragma unroll
-          for (int kk = 0; kk < 2; kk++) fb[j][kk] = __builtin_bit_cast(bf16x8, relu_bf16x8(__builtin_bit_cast(u32x4, fb[j][kk])));
-      }
-      __builtin_amdgcn_sched_barrier(0);               // keeps the MFMA cluster behind the barrier (hipcc hoists it otherwise)
-#pragma unroll
-      for (int kk = 0; kk < 2; kk++)
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-          for (int j = 0; j < 4; j++)
-            acc[i][j] = GANK_MFMA32(fa[i][kk], fb[j][kk], acc[i][j]);
-#endif
       __builtin_amdgcn_sched_barrier(0);
       rslot += PP_WSLOT_BYTES; if (rslot == PP_NSLOT * PP_WSLOT_BYTES) rslot = 0;
       wslot += PP_WSLOT_BYTES; if (wslot == PP_NSLOT * PP_WSLOT_BYTES) wslot = 0;
@@ -1449,7 +1347,6 @@ __global__ __launch_bounds__(512) void conv_igemm_pp_kernel(IgemmArgs a) {
   // in fp32 wants a small mean.  A wave reduces its 32 pixels by shuffles; lanes r = 0 add to one of GANK_STAT_SLOTS copies
   // of the tower's sums (blocks of a tower spread over the copies: same-address float atomics serialise at the memory side).
   float keep1 = 0.f, keep2 = 0.f;
-#if GANK_PP_M16
   // 16x16x32 accumulators: lane (p16, kc) of tile (i, j) holds couts 4 kc .. 4 kc + 3 of pixel p16 (8 bytes).  For a PAIR of
   // cout tiles (2P, 2P+1), v_permlane16_swap with vdst = tile 2P's register and src = tile 2P+1's trades the odd 16-lane rows
   // of the one for the even rows of the other: afterwards row kc owns 8 CONSECUTIVE couts 8 (kc >> 1) .. + 7 of tile
@@ -1529,108 +1426,9 @@ __global__ __launch_bounds__(512) void conv_igemm_pp_kernel(IgemmArgs a) {
     // ONE full-width atomic per statistic and wave: lane (p16, kc) carries channel (P, e) = (p16 >> 3, p16 & 7) of its row
     float* dst = a.stat_sums + ((long)(n / a.stat_n_per_group) * GANK_STAT_SLOTS + (blockIdx.x % GANK_STAT_SLOTS)) * 2 * a.Cout;
     const int co = tile_n * 256 + wn * 64 + (2 * (p16 >> 3) + (kc & 1)) * 16 + 8 * (kc >> 1) + (p16 & 7);
-#ifdef GANK_TUNING
-    if (gank_stats_dbg) return;
-#endif
     atomicAdd(dst + co, keep1);
     atomicAdd(dst + a.Cout + co, keep2);
   }
-#else
-  {
-    // all 64 running sums are live beside the accumulators (200 VGPRs; holding the packed results for a separate store pass
-    // instead spilled 22-25 of them)
-    float st1[STATS ? 2 : 1][2][8], st2[STATS ? 2 : 1][2][8];
-    if constexpr (STATS) {
-#pragma unroll
-      for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int q = 0; q < 2; q++)
-#pragma unroll
-          for (int e = 0; e < 8; e++) { st1[i][q][e] = 0.f; st2[i][q][e] = 0.f; }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int py = py0 + wm * (PHH / 2) + j * RS + prow, px = px0 + pcol;
-      const long m = PHASE ? ((long)(n * 2 * a.H + 2 * py + (phase >> 1))) * (2 * a.W) + 2 * px + (phase & 1) : ((long)(n * a.H + py)) * a.W + px;
-      const long mr = (!PHASE && (a.flags & IG_RES_UP2X)) ? ((long)(n * (a.H >> 1) + (py >> 1))) * (a.W >> 1) + (px >> 1) : m;
-      bf16x8 outl[2][2];
-#pragma unroll
-      for (int i = 0; i < 2; i++) {
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-          const int co = tile_n * 256 + (wn * 2 + i) * 32 + 16 * q + 8 * h;
-          float v[8];
-#pragma unroll
-          for (int e = 0; e < 4; e++) {
-            float lo = acc[i][j][8 * q + e] * a.scale, hi = acc[i][j][8 * q + 4 + e] * a.scale;
-            asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lo), "+v"(hi));
-            v[e] = lo;
-            v[4 + e] = hi;
-          }
-          const long o = m * a.Cout + co;
-          // y in the operation order of the plain variant (bit-identical outputs); the statistics are of d = y - bias,
-          // carried beside it without ever adding the bias
-          float bb[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, d[8];
-          if (a.bias) {
-            const f32x4 b0 = *reinterpret_cast<const f32x4*>(a.bias + co), b1 = *reinterpret_cast<const f32x4*>(a.bias + co + 4);
-#pragma unroll
-            for (int e = 0; e < 4; e++) { bb[e] = b0[e]; bb[4 + e] = b1[e]; }
-          }
-#pragma unroll
-          for (int e = 0; e < 8; e++) { d[e] = v[e]; v[e] += bb[e]; }
-          if (a.mask) {
-            const bf16x8 mk = *reinterpret_cast<const bf16x8*>(a.mask + o);
-#pragma unroll
-            for (int e = 0; e < 8; e++) { const bool on = bf2f(mk[e]) > 0.f; v[e] = on ? v[e] : 0.f; d[e] = on ? d[e] : -bb[e]; }
-          }
-          if (a.res) {
-            const bf16x8 rs = *reinterpret_cast<const bf16x8*>(a.res + mr * a.Cout + co);
-#pragma unroll
-            for (int e = 0; e < 8; e++) { const float t = bf2f(rs[e]); v[e] += t; d[e] += t; }
-          }
-          if constexpr (STATS) {
-#pragma unroll
-            for (int e = 0; e < 8; e++) { st1[i][q][e] += d[e]; st2[i][q][e] += d[e] * d[e]; }
-          }
-#pragma unroll
-          for (int e = 0; e < 8; e++) outl[i][q][e] = f2bf(otanh ? tanhf(v[e]) : v[e]);
-        }
-      }
-      bf16* line = a.y + m * a.Cout + tile_n * 256 + wn * 64 + 8 * h;
-#pragma unroll
-      for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int q = 0; q < 2; q++) *reinterpret_cast<bf16x8*>(line + i * 32 + 16 * q) = outl[i][q];
-    }
-    if constexpr (STATS) {
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int q = 0; q < 2; q++)
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-          float s1 = pp_row_sum(st1[i][q][e]), s2 = pp_row_sum(st2[i][q][e]);
-          s1 += __shfl_xor(s1, 16, 64);
-          s2 += __shfl_xor(s2, 16, 64);
-          const bool mine = r == (2 * i + q) * 8 + e;
-          keep1 = mine ? s1 : keep1;
-          keep2 = mine ? s2 : keep2;
-        }
-    }
-  }
-  if constexpr (STATS) {
-    // ONE full-width atomic per statistic and wave (an atomic instruction costs the memory pipe the same with 2 lanes as
-    // with 64: 512 two-lane atomics per block made this epilogue slower than the statistics pass it replaces)
-    float* dst = a.stat_sums + ((long)(n / a.stat_n_per_group) * GANK_STAT_SLOTS + (blockIdx.x % GANK_STAT_SLOTS)) * 2 * a.Cout;
-    const int ci = r >> 4, cq = (r >> 3) & 1, ce = r & 7;
-    const int co = tile_n * 256 + (wn * 2 + ci) * 32 + 16 * cq + 8 * h + ce;
-#ifdef GANK_TUNING
-    if (gank_stats_dbg) return;
-#endif
-    atomicAdd(dst + co, keep1);
-    atomicAdd(dst + a.Cout + co, keep2);
-  }
-#endif
 }
 
 static thread_local int tl_stats_done = 0;     // did the kernel chosen by the last dispatch accumulate a.stat_sums?
@@ -1641,15 +1439,11 @@ __global__ void ig_zero_kernel(float* __restrict__ p, int n) {
 
 static void stats_zero(const IgemmArgs& a, hipStream_t s);
 // 128x128 tiles from this many tiles on; fewer run as 64x64 (4x the workgroups: the grid rounds better on 256 CUs)
-static int t128_min() {
-  static const int v = gank_tune("GANK_IGEMM_T128_MIN", 192);   // experiment knob
-  return v;
-}
+constexpr int T128_MIN = 192;
 // generic kernel with the statistics epilogue: every pixel tile full and inside one tower, every channel tile full
 // (a.M, a.H, a.W: the grid the tiles walk -- the low-resolution grid in phase mode)
 static bool igemm_stats_ok(const IgemmArgs& a, int BM, int BN) {
-  static const int env = gank_tune("GANK_IGEMM_STATS", 1);   // experiment knob: GANK_IGEMM_STATS=0 leaves the statistics to the batch-norm kernels
-  return env && a.stat_sums != nullptr && !(a.flags & GANK_OUT_TANH) && a.M % BM == 0 && a.Cout % BN == 0 &&
+  return a.stat_sums != nullptr && !(a.flags & GANK_OUT_TANH) && a.M % BM == 0 && a.Cout % BN == 0 &&
          ((long)a.stat_n_per_group * a.H * a.W) % BM == 0;
 }
 template <int MODE, int PW>
@@ -1660,7 +1454,7 @@ static int launch_pp(const IgemmArgs& a0, hipStream_t s) {
   constexpr bool PHASE = (MODE & 4) != 0;
   const int tiles = a.N * (a.H / (256 / PW)) * (a.W / PW);
   a.tiles_pp = tiles;
-  a.phase_inner = phase_inner_env();
+  a.phase_inner = 1;
   a.tiles_m = PHASE ? 4 * tiles : tiles;
   a.tiles_n = a.Cout / 256;
   if (PHASE) { a.Kpad = 4 * a.Cin; a.Hin = a.H; a.Win = a.W; }
@@ -1675,10 +1469,6 @@ static int launch_pp(const IgemmArgs& a0, hipStream_t s) {
 }
 // geometry both PP forms need (H, W = the grid the patches tile: the output for a plain conv, the low-res grid in phase mode)
 static int pp_patch_width(int H, int W) { return (W % 32 == 0 && H % 8 == 0) ? 32 : (W % 16 == 0 && H % 16 == 0) ? 16 : 0; }
-static int pp_env() {          // GANK_IGEMM_PP: 0 off, 1 32-wide patches of plain convs only, 2 (default) every form
-  static const int v = gank_tune("GANK_IGEMM_PP", 2);
-  return v;
-}
 // One 512-thread block per CU: below ~a full round of blocks the 128-wide kernels (2-3 blocks per CU) fill the chip better
 // (16 x 16 images, n = 128: 128 blocks, 49.6 us against 43.9).
 static bool pp_enough_blocks(const IgemmArgs& a, int phases) {
@@ -1686,7 +1476,7 @@ static bool pp_enough_blocks(const IgemmArgs& a, int phases) {
   return pw != 0 && (long)phases * a.N * (a.H / (256 / pw)) * (a.W / pw) * (a.Cout / 256) >= 224;
 }
 static bool pp_phase_ok(const IgemmArgs& a) {   // a.H, a.W = low-res grid
-  return pp_env() >= 2 && a.Cout % 256 == 0 && a.Cin % 32 == 0 && pp_enough_blocks(a, 4);
+  return a.Cout % 256 == 0 && a.Cin % 32 == 0 && pp_enough_blocks(a, 4);
 }
 static int launch_pp_phase(const IgemmArgs& a, hipStream_t s) {
   const bool relu = (a.flags & GANK_IN_RELU) != 0;
@@ -1741,7 +1531,7 @@ static int launch_phase(const IgemmArgs& a0, hipStream_t s) {
   IgemmArgs a = a0;
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   a.tiles_pp = cdiv(a.M, BM);
-  a.phase_inner = phase_inner_env();
+  a.phase_inner = 1;
   a.tiles_m = 4 * a.tiles_pp;
   a.tiles_n = a.CoutPad / BN;
   const size_t lds = (size_t)2 * (BM + BN) * LROW * sizeof(bf16);
@@ -1797,19 +1587,15 @@ int gank_igemm_dispatch(IgemmArgs a, hipStream_t s) {
                                       (a.res ? (double)a.M * a.Cout / ((a.flags & IG_RES_UP2X) ? 4.0 : 1.0) : 0.0) + (a.mask ? (double)a.M * a.Cout : 0.0)));
   int rc;
   const long tiles128 = (long)cdiv(a.M, 128) * (a.CoutPad / 128);
-  static const int ko_env = gank_tune("GANK_IGEMM_KORDER", 0);
-  a.korder = ko_env;
-  static const int pf_env = gank_tune("GANK_IGEMM_PF", 0);   // experiment knob: GANK_IGEMM_PF=1|2|3 overrides the prefetch depth
-  static const int patch_env = gank_tune("GANK_IGEMM_PATCH", 1);   // experiment knob: GANK_IGEMM_PATCH=0 disables the LDS-patch kernel
-  const bool patch_geom = patch_env && !packed && a.ks == 3 && a.pad == 1 &&
+  a.korder = 0;   // tap outer, channel chunk inner
+  const bool patch_geom = !packed && a.ks == 3 && a.pad == 1 &&
                           !(a.flags & (GANK_IN_UPSAMPLE2X | IG_IN_ZEROINS2X | IG_IN_STRIDE2)) &&
                           a.W % 16 == 0 && a.H % 8 == 0 && a.Hin == a.H && a.Win == a.W;
   const bool patch_ok = patch_geom && (a.Cout % 4) == 0 && a.CoutPad % 128 == 0;
   const bool patch32_ok = patch_geom && a.CoutPad == 32;
   const bool narrow_ok = !(a.flags & IG_RES_UP2X) && a.Cin == 3 && (a.ks == 1 || a.ks == 3) && a.pad == (a.ks - 1) / 2 && a.CoutPad % 128 == 0 && a.Cout % 4 == 0 &&
                          !(a.flags & (GANK_IN_UPSAMPLE2X | IG_IN_ZEROINS2X | IG_IN_STRIDE2)) && a.Hin == a.H && a.Win == a.W;
-  const bool pp_ok = pp_env() && patch_geom && a.Cout % 256 == 0 && a.Kpad == a.taps * a.Cin && pp_enough_blocks(a, 1) &&
-                     (pp_env() >= 2 || pp_patch_width(a.H, a.W) == 32);
+  const bool pp_ok = patch_geom && a.Cout % 256 == 0 && a.Kpad == a.taps * a.Cin && pp_enough_blocks(a, 1);
   if (narrow_ok) {
     rc = a.ks == 3 ? launch_narrow_in<3, 3>(a, s) : launch_narrow_in<1, 3>(a, s);
   } else if (pp_ok) {
@@ -1825,18 +1611,7 @@ int gank_igemm_dispatch(IgemmArgs a, hipStream_t s) {
   } else if (packed) {
     if (a.CoutPad % 64 == 0) rc = launch_cfg<2, 2, 1, 1, true, 1, 0>(a, s);
     else rc = launch_cfg<4, 1, 2, 1, true, 1, 0>(a, s);
-#ifdef GANK_TUNING          // tile shapes and prefetch depths that lost their A/B runs: only an experiment build instantiates them
-  } else if (a.CoutPad % 128 == 0 && tiles128 >= t128_min() && pf_env >= 20) {
-    if (pf_env == 20) rc = launch_mode<4, 2, 2, 2, 1>(a, s);          // 256 x 128, 8 waves
-    else if (pf_env == 22 && a.CoutPad % 256 == 0) rc = launch_mode<2, 4, 2, 2, 2>(a, s);   // 128 x 256
-    else if (pf_env == 23 && a.CoutPad % 256 == 0) rc = launch_mode<4, 2, 2, 4, 2>(a, s);   // 256 x 256, wave 64x128
-    else rc = launch_mode<4, 2, 2, 2, 2>(a, s);
-  } else if (a.CoutPad % 128 == 0 && tiles128 >= t128_min() && (pf_env == 1 || pf_env == 3)) {
-    rc = pf_env == 1 ? launch_mode<2, 2, 2, 2, 1>(a, s) : launch_mode<2, 2, 2, 2, 3>(a, s);
-  } else if (a.CoutPad % 64 == 0 && !(a.CoutPad % 128 == 0 && tiles128 >= t128_min()) && (pf_env == 1 || pf_env == 11 || pf_env == 12 || pf_env == 3)) {
-    rc = (pf_env == 1 || pf_env == 11) ? launch_mode<2, 2, 1, 1, 1>(a, s) : launch_mode<2, 2, 1, 1, 2>(a, s);
-#endif
-  } else if (a.CoutPad % 128 == 0 && tiles128 >= t128_min()) {
+  } else if (a.CoutPad % 128 == 0 && tiles128 >= T128_MIN) {
     rc = launch_mode<2, 2, 2, 2, 2>(a, s);               // 128 x 128 tiles, prefetch depth 2
   } else if (a.CoutPad % 64 == 0) {
     rc = launch_mode<2, 2, 1, 1, 4>(a, s);               // 64 x 64 tiles (4x the workgroups: small grids round better on 256 CUs), depth 4
@@ -1850,7 +1625,6 @@ int gank_igemm_dispatch(IgemmArgs a, hipStream_t s) {
 static int stats_setup(IgemmArgs& a, float* stat_sums, int groups, int N, int Cout, hipStream_t s, int flags) {
   tl_stats_done = 0;
   if (!stat_sums) return 0;
-  gank_stats_dbg_init();
   a.stat_prezeroed = (flags & GANK_STATS_PREZEROED) != 0;
   GANK_REQUIRE(groups > 0 && N % groups == 0, "conv statistics: batch %d not divisible by %d towers", N, groups);
   a.stat_sums = stat_sums;
@@ -1961,7 +1735,7 @@ extern "C" int gank_image_conv_pair_fprop(const void* x, const void* wf1, const 
   a.taps = 9; a.CoutPad = Cout1; a.Kpad = roundup(27, 64); a.nsteps = 1;
   a.M = N * H * W; a.sw = log2_or_neg(W); a.shw = log2_or_neg(H * W);
   a.tiles_m = cdiv(a.M, 128); a.tiles_n = a.CoutPad / 128;
-  { static const int ko_env = gank_tune("GANK_IGEMM_KORDER", 0); a.korder = ko_env; }
+  a.korder = 0;
   const int Hp = H / 2, Wp = W / 2;
   b.x = (const bf16*)x; b.w = (const bf16*)wfs; b.bias = biass; b.y = (bf16*)ys; b.aux_out = (bf16*)pooled;
   b.N = N; b.H = Hp; b.W = Wp; b.Hin = H; b.Win = W; b.Cin = 3; b.Cout = Couts; b.ks = 1; b.pad = 0; b.scale = 1.f;
@@ -2054,7 +1828,7 @@ static int upconv3x3_fprop_impl(const void* x, const void* wph, const float* bia
   const long tiles128 = 4L * cdiv(a.M, 128) * (a.CoutPad / 128);
   if (pp_phase_ok(a)) rc = launch_pp_phase(a, s);
   else if (patch_phase_ok(a)) rc = launch_patch_phase<4>(a, s);
-  else if (a.CoutPad % 128 == 0 && tiles128 >= t128_min()) rc = launch_phase<2, 2, 2, 2, 2>(a, s);
+  else if (a.CoutPad % 128 == 0 && tiles128 >= T128_MIN) rc = launch_phase<2, 2, 2, 2, 2>(a, s);
   else if (a.CoutPad % 64 == 0) rc = launch_phase<2, 2, 1, 1, 4>(a, s);
   else rc = launch_phase<4, 1, 2, 1, 2>(a, s);
   gank_prof_end(0, s);
@@ -2121,7 +1895,7 @@ extern "C" int gank_convpool3x3_dgrad(const void* dy, const void* wphd, const vo
   const long tiles128 = 4L * cdiv(a.M, 128) * (a.CoutPad / 128);
   if (pp_phase_ok(a)) rc = launch_pp_phase(a, s);
   else if (patch_phase_ok(a)) rc = launch_patch_phase<4>(a, s);
-  else if (a.CoutPad % 128 == 0 && tiles128 >= t128_min()) rc = launch_phase<2, 2, 2, 2, 2>(a, s);
+  else if (a.CoutPad % 128 == 0 && tiles128 >= T128_MIN) rc = launch_phase<2, 2, 2, 2, 2>(a, s);
   else if (a.CoutPad % 64 == 0) rc = launch_phase<2, 2, 1, 1, 4>(a, s);
   else rc = launch_phase<4, 1, 2, 1, 2>(a, s);
   gank_prof_end(0, s);

@@ -19,17 +19,6 @@
 // Wave ct of the 4: output channels 32*ct .. +31 of all 64 pixels (two MFMA tiles: image rows 0-3, 4-7).
 #include "gank_common.h"
 #include "label_conv_dev.h"
-#ifdef GANK_TUNING
-// timing-only experiment (GANK_STATS_DBG=1): the statistics epilogues skip their atomics (set once per process, before the first launch)
-static __device__ int gank_stats_dbg = 0;
-static void gank_stats_dbg_init() {
-  static const int v = gank_tune("GANK_STATS_DBG", 0);
-  static bool done = false;
-  if (!done) { done = true; if (v) (void)hipMemcpyToSymbol(HIP_SYMBOL(gank_stats_dbg), &v, sizeof(int)); }
-}
-#else
-static inline void gank_stats_dbg_init() {}
-#endif
 #include <stdlib.h>
 
 namespace {
@@ -89,29 +78,29 @@ __device__ __forceinline__ void res_head_term(float v, int m, int M, int n_real,
   dl = bf2f(f2bf(d * loss_scale));
 }
 
-// TPW = 32-pixel MFMA tiles per wave (1: 8 waves per sample, 2: 4 waves, every weight fragment feeds two MFMAs);
-// PF = weight fragments in flight per wave.  A wave consumes one 1 KB fragment per TPW x 32 MFMA cycles and an L2 hit
-// takes 500+ cycles under load, so PF x TPW x 32 must cover that: 8 in flight left the matrix pipe waiting.
+// TPW = 32-pixel MFMA tiles per wave (every weight fragment feeds two MFMAs); PF = weight fragments in flight per wave.
+// A wave consumes one 1 KB fragment per TPW x 32 MFMA cycles and an L2 hit takes 500+ cycles under load, so PF x TPW x 32
+// must cover that: 8 in flight left the matrix pipe waiting.
 // The weight stream never stops: the ring is filled once (res_ring_fill) and the last PF steps of a conv already
 // request the first PF fragments of the NEXT conv (`rn`), so the L2 round trip of a conv's first fragments hides behind
 // the previous conv's tail, its epilogue and the barrier instead of opening every conv with an idle matrix pipe.
-template <int PF>
-__device__ __forceinline__ void res_ring_fill(u32x4 (&ring)[PF], const __amdgpu_buffer_rsrc_t rw, int lane16, int wbase) {
+constexpr int RB_TPW = 2, RB_PF = 12, RB_NT = 512;         // (4 channel tiles) x (2 halves of the reduction) waves
+__device__ __forceinline__ void res_ring_fill(u32x4 (&ring)[RB_PF], const __amdgpu_buffer_rsrc_t rw, int lane16, int wbase) {
 #pragma unroll
-  for (int s = 0; s < PF; s++) ring[s] = __builtin_amdgcn_raw_buffer_load_b128(rw, lane16, wbase + s * 1024, 0);
+  for (int s = 0; s < RB_PF; s++) ring[s] = __builtin_amdgcn_raw_buffer_load_b128(rw, lane16, wbase + s * 1024, 0);
 }
-// S0, NS: this wave's share of the K-steps (all of them, or one half when the reduction is split over two wave groups:
-// `wbase` then already points at step S0 of the wave's fragment stream)
-template <bool RELU, int TPW, int PF, int S0 = 0, int NS = RB_STEPS>
-__device__ __forceinline__ void res_conv3x3(f32x16 (&acc)[TPW], u32x4 (&ring)[PF], const char* smem, int b_base, const __amdgpu_buffer_rsrc_t rw,
+// S0, NS: this wave's share of the K-steps (one half: the reduction is split over two wave groups and `wbase` already points
+// at step S0 of the wave's fragment stream)
+template <bool RELU, int S0, int NS>
+__device__ __forceinline__ void res_conv3x3(f32x16 (&acc)[RB_TPW], u32x4 (&ring)[RB_PF], const char* smem, int b_base, const __amdgpu_buffer_rsrc_t rw,
                                             const __amdgpu_buffer_rsrc_t rn, bool has_next, int lane16, int wbase) {
-  static_assert(NS % PF == 0, "the ring position must be the same at the start of every conv");
+  static_assert(NS % RB_PF == 0, "the ring position must be the same at the start of every conv");
   constexpr int PB = 2;                              // pixel fragments are read PB steps ahead of their MFMAs
-  u32x4 bq[PB + 1][TPW];
-  auto read_b = [&](int s, u32x4 (&dst)[TPW]) {
+  u32x4 bq[PB + 1][RB_TPW];
+  auto read_b = [&](int s, u32x4 (&dst)[RB_TPW]) {
     const int tap = (S0 + s) >> 3, kk = (S0 + s) & 7;
 #pragma unroll
-    for (int t = 0; t < TPW; t++)
+    for (int t = 0; t < RB_TPW; t++)
       dst[t] = *reinterpret_cast<const u32x4*>(smem + b_base + (4 * t + tap / 3) * RB_RPB + (tap % 3) * RB_PPB + kk * 32);
   };
 #pragma unroll
@@ -121,100 +110,91 @@ __device__ __forceinline__ void res_conv3x3(f32x16 (&acc)[TPW], u32x4 (&ring)[PF
     // sched_barrier: hipcc otherwise sinks the LDS reads to just in front of their MFMAs (lgkmcnt(0) before every pair,
     // the whole LDS latency exposed) and lets only ~5 weight requests stay in flight
     if (s + PB < NS) read_b(s + PB, bq[(s + PB) % (PB + 1)]);
-    const bf16x8 fa = __builtin_bit_cast(bf16x8, ring[s % PF]);
+    const bf16x8 fa = __builtin_bit_cast(bf16x8, ring[s % RB_PF]);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int t = 0; t < TPW; t++) {
+    for (int t = 0; t < RB_TPW; t++) {
       u32x4 bv = bq[s % (PB + 1)][t];
       if constexpr (RELU) bv = relu_bf16x8(bv);
       acc[t] = GANK_MFMA32(fa, __builtin_bit_cast(bf16x8, bv), acc[t]);
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (s + PF < NS) ring[s % PF] = __builtin_amdgcn_raw_buffer_load_b128(rw, lane16, wbase + (s + PF) * 1024, 0);
-    else if (has_next) ring[s % PF] = __builtin_amdgcn_raw_buffer_load_b128(rn, lane16, wbase + (s + PF - NS) * 1024, 0);
+    if (s + RB_PF < NS) ring[s % RB_PF] = __builtin_amdgcn_raw_buffer_load_b128(rw, lane16, wbase + (s + RB_PF) * 1024, 0);
+    else if (has_next) ring[s % RB_PF] = __builtin_amdgcn_raw_buffer_load_b128(rn, lane16, wbase + (s + RB_PF - NS) * 1024, 0);
     __builtin_amdgcn_sched_barrier(0);
   }
 }
-// one conv of a chain kernel: KS == 1 -> every wave runs all K-steps; KS == 2 -> wave group kg runs its half (a wave-uniform branch
+// one conv of a chain kernel: wave group kg runs its half of the K-steps (a wave-uniform branch
 // between two fully unrolled bodies, so the LDS offsets stay immediates), the two partial tiles meet in `part` (LDS behind the
-// images: [4 channel tiles][2 * TPW * 4 quads][64 lanes] x 16 B, consecutive lanes contiguous): group 1 parks its sums, a
+// images: [4 channel tiles][2 * RB_TPW * 4 quads][64 lanes] x 16 B, consecutive lanes contiguous): group 1 parks its sums, a
 // barrier, group 0 adds them -- after this call only kg == 0 holds the result
-template <bool RELU, int TPW, int PF, int KS>
-__device__ __forceinline__ void res_conv3x3_ks(f32x16 (&acc)[TPW], u32x4 (&ring)[PF], const char* smem, int b_base, const __amdgpu_buffer_rsrc_t rw,
+template <bool RELU>
+__device__ __forceinline__ void res_conv3x3_ks(f32x16 (&acc)[RB_TPW], u32x4 (&ring)[RB_PF], const char* smem, int b_base, const __amdgpu_buffer_rsrc_t rw,
                                                const __amdgpu_buffer_rsrc_t rn, bool has_next, int lane16, int wbase, int kg, f32x4* part, int lane) {
-  if constexpr (KS == 1) {
-    res_conv3x3<RELU, TPW, PF>(acc, ring, smem, b_base, rw, rn, has_next, lane16, wbase);
-  } else {
-    constexpr int NS = RB_STEPS / 2;
-    if (kg == 0) res_conv3x3<RELU, TPW, PF, 0, NS>(acc, ring, smem, b_base, rw, rn, has_next, lane16, wbase);
-    else res_conv3x3<RELU, TPW, PF, NS, NS>(acc, ring, smem, b_base, rw, rn, has_next, lane16, wbase);
-    if (kg == 1) {
+  constexpr int NS = RB_STEPS / 2;
+  if (kg == 0) res_conv3x3<RELU, 0, NS>(acc, ring, smem, b_base, rw, rn, has_next, lane16, wbase);
+  else res_conv3x3<RELU, NS, NS>(acc, ring, smem, b_base, rw, rn, has_next, lane16, wbase);
+  if (kg == 1) {
 #pragma unroll
-      for (int t = 0; t < TPW; t++)
+    for (int t = 0; t < RB_TPW; t++)
 #pragma unroll
-        for (int g = 0; g < 4; g++) part[(t * 4 + g) * 64 + lane] = f32x4{acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]};
-    }
-    __syncthreads();
-    if (kg == 0) {
+      for (int g = 0; g < 4; g++) part[(t * 4 + g) * 64 + lane] = f32x4{acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]};
+  }
+  __syncthreads();
+  if (kg == 0) {
 #pragma unroll
-      for (int t = 0; t < TPW; t++)
+    for (int t = 0; t < RB_TPW; t++)
 #pragma unroll
-        for (int g = 0; g < 4; g++) {
-          const f32x4 o = part[(t * 4 + g) * 64 + lane];
+      for (int g = 0; g < 4; g++) {
+        const f32x4 o = part[(t * 4 + g) * 64 + lane];
 #pragma unroll
-          for (int e = 0; e < 4; e++) acc[t][4 * g + e] += o[e];
-        }
-    }
+        for (int e = 0; e < 4; e++) acc[t][4 * g + e] += o[e];
+      }
   }
 }
 
 // interior of an image <-> [64 pixels][C] in HBM, 16 bytes per lane, whole 256-byte pixel rows
-template <int NT>
 __device__ __forceinline__ void res_store_image(const char* img, bf16* dst, int tid) {
 #pragma unroll
-  for (int it = 0; it < 1024 / NT; it++) {
-    const int q = tid + it * NT, px = q >> 4, c16 = q & 15;
+  for (int it = 0; it < 1024 / RB_NT; it++) {
+    const int q = tid + it * RB_NT, px = q >> 4, c16 = q & 15;
     *reinterpret_cast<u32x4*>(dst + px * RB_C + c16 * 8) =
         *reinterpret_cast<const u32x4*>(img + ((px >> 3) + 1) * RB_RPB + ((px & 7) + 1) * RB_PPB + c16 * 16);
   }
 }
-template <int NT>
 __device__ __forceinline__ void res_load_image(char* img, const bf16* src, int tid) {
 #pragma unroll
-  for (int it = 0; it < 1024 / NT; it++) {
-    const int q = tid + it * NT, px = q >> 4, c16 = q & 15;
+  for (int it = 0; it < 1024 / RB_NT; it++) {
+    const int q = tid + it * RB_NT, px = q >> 4, c16 = q & 15;
     *reinterpret_cast<u32x4*>(img + ((px >> 3) + 1) * RB_RPB + ((px & 7) + 1) * RB_PPB + c16 * 16) =
         *reinterpret_cast<const u32x4*>(src + px * RB_C + c16 * 8);
   }
 }
 }  // namespace
 
-// KS = 2 (with TPW = 2): the 8 waves are (4 channel tiles) x (2 halves of the reduction) instead of x (2 pixel tiles): every
+// The 8 waves are (4 channel tiles) x (2 halves of the reduction) instead of x (2 pixel tiles): every
 // weight fragment is then requested by ONE wave of the workgroup and feeds two MFMAs, instead of being requested by two waves
 // for one MFMA each -- the CU's L1 path carried every weight byte twice, and that path (not L2, not the matrix pipe) bounds
 // these kernels.  The halves meet in LDS after each conv (res_conv3x3_ks).
-template <int TPW, int PF, int KS>
-__global__ __launch_bounds__(512 / TPW * KS) void res8_chain_fwd_kernel(ResFwdArgs a) {
-  constexpr int NT = 512 / TPW * KS;
-  static_assert(KS == 1 || TPW == 2, "the K split needs both pixel tiles in one wave");
+__global__ __launch_bounds__(RB_NT) void res8_chain_fwd_kernel(ResFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ct = wave & 3;                                                        // 32 output channels per wave
-  const int kg = KS == 2 ? wave >> 2 : 0;
+  const int kg = wave >> 2;
   const int r = lane & 31, h = lane >> 5;
   const long n = blockIdx.x;
-  const int row = (KS == 2 ? 0 : 4 * (wave >> 2)) + (r >> 3), col = r & 7;        // pixel of this wave's first tile; tile t = 4 t rows below
+  const int row = (r >> 3), col = r & 7;        // pixel of this wave's first tile; tile t = 4 t rows below
   const int b_base = row * RB_RPB + col * RB_PPB + h * 16;                        // tap (0,0), kk 0 of this lane's pixel
   const int own = (row + 1) * RB_RPB + (col + 1) * RB_PPB + ct * 64 + h * 8;      // this lane's 4 channels of quad g: + 16 g (+ 4 rows for tile 1)
   const int wbase = (ct * RB_STEPS + kg * (RB_STEPS / 2)) * 1024;
-  f32x4* part = reinterpret_cast<f32x4*>(smem + RB_LDS) + ct * (TPW * 4 * 64);
+  f32x4* part = reinterpret_cast<f32x4*>(smem + RB_LDS) + ct * (RB_TPW * 4 * 64);
 
-  u32x4 ring[PF];
-  res_ring_fill<PF>(ring, __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(a.w[0]), 0, RB_WBYTES, 0x00020000), lane * 16, wbase);
-  for (int i = tid; i < RB_LDS / 16; i += NT) reinterpret_cast<u32x4*>(smem)[i] = u32x4{0u, 0u, 0u, 0u};
+  u32x4 ring[RB_PF];
+  res_ring_fill(ring, __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(a.w[0]), 0, RB_WBYTES, 0x00020000), lane * 16, wbase);
+  for (int i = tid; i < RB_LDS / 16; i += RB_NT) reinterpret_cast<u32x4*>(smem)[i] = u32x4{0u, 0u, 0u, 0u};
   __syncthreads();
-  res_load_image<NT>(smem, a.x + n * 64 * RB_C, tid);
+  res_load_image(smem, a.x + n * 64 * RB_C, tid);
   __syncthreads();
 
 #pragma unroll 1
@@ -231,15 +211,15 @@ __global__ __launch_bounds__(512 / TPW * KS) void res8_chain_fwd_kernel(ResFwdAr
     const bool more = b + 1 < a.nblocks;             // a.w[2] is the next block's conv_1 (a valid pointer is needed only then)
     const __amdgpu_buffer_rsrc_t r3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(more ? a.w[2] : w2), 0, RB_WBYTES, 0x00020000);
 
-    f32x16 acc[TPW];
+    f32x16 acc[RB_TPW];
 #pragma unroll
-    for (int t = 0; t < TPW; t++)
+    for (int t = 0; t < RB_TPW; t++)
 #pragma unroll
       for (int e = 0; e < 16; e++) acc[t][e] = 0.f;
-    res_conv3x3_ks<true, TPW, PF, KS>(acc, ring, smem, b_base, r1, r2, true, lane * 16, wbase, kg, part, lane);   // conv_1(relu(x))      (:186-190)
+    res_conv3x3_ks<true>(acc, ring, smem, b_base, r1, r2, true, lane * 16, wbase, kg, part, lane);   // conv_1(relu(x))      (:186-190)
     if (kg == 0) {
 #pragma unroll
-    for (int t = 0; t < TPW; t++)
+    for (int t = 0; t < RB_TPW; t++)
 #pragma unroll
       for (int g = 0; g < 4; g++) {
         f32x4 bb = {0.f, 0.f, 0.f, 0.f};
@@ -251,15 +231,15 @@ __global__ __launch_bounds__(512 / TPW * KS) void res8_chain_fwd_kernel(ResFwdAr
       }
     }
     __syncthreads();                                                              // image B = h1 complete
-    if (h1) res_store_image<NT>(smem + RB_IMG, h1 + n * 64 * RB_C, tid);
+    if (h1) res_store_image(smem + RB_IMG, h1 + n * 64 * RB_C, tid);
 #pragma unroll
-    for (int t = 0; t < TPW; t++)
+    for (int t = 0; t < RB_TPW; t++)
 #pragma unroll
       for (int e = 0; e < 16; e++) acc[t][e] = 0.f;
-    res_conv3x3_ks<true, TPW, PF, KS>(acc, ring, smem + RB_IMG, b_base, r2, r3, more, lane * 16, wbase, kg, part, lane);   // conv_2(relu(h1))     (:198-207)
+    res_conv3x3_ks<true>(acc, ring, smem + RB_IMG, b_base, r2, r3, more, lane * 16, wbase, kg, part, lane);   // conv_2(relu(h1))     (:198-207)
     if (kg == 0) {
 #pragma unroll
-    for (int t = 0; t < TPW; t++)
+    for (int t = 0; t < RB_TPW; t++)
 #pragma unroll
       for (int g = 0; g < 4; g++) {
         f32x4 bb = {0.f, 0.f, 0.f, 0.f};
@@ -272,7 +252,7 @@ __global__ __launch_bounds__(512 / TPW * KS) void res8_chain_fwd_kernel(ResFwdAr
       }
     }
     __syncthreads();                                                              // image A = y complete
-    if (y) res_store_image<NT>(smem, y + n * 64 * RB_C, tid);
+    if (y) res_store_image(smem, y + n * 64 * RB_C, tid);
   }
   float* sp = reinterpret_cast<float*>(smem + RB_IMG);                            // image B is dead here: [C] pooled values for the head
   if (a.pooled && tid < RB_C) {                                                   // relu + mean over the 8 x 8 pixels (:299-301)
@@ -295,15 +275,12 @@ __global__ __launch_bounds__(512 / TPW * KS) void res8_chain_fwd_kernel(ResFwdAr
   }
 }
 
-template <int TPW, int PF, int KS>
-__global__ __launch_bounds__(512 / TPW * KS) void res8_chain_bwd_kernel(ResBwdArgs a) {
-  constexpr int NT = 512 / TPW * KS;
-  static_assert(KS == 1 || TPW == 2, "the K split needs both pixel tiles in one wave");
+__global__ __launch_bounds__(RB_NT) void res8_chain_bwd_kernel(ResBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ct = wave & 3;
-  const int kg = KS == 2 ? wave >> 2 : 0;
+  const int kg = wave >> 2;
   const int r = lane & 31, h = lane >> 5;
   const long n = blockIdx.x;
   if (a.logits && n == a.N) {                        // the workgroup behind the samples: loss value, D.Output's weight / bias gradient
@@ -311,7 +288,7 @@ __global__ __launch_bounds__(512 / TPW * KS) void res8_chain_bwd_kernel(ResBwdAr
     float* red = s_dl + a.N;                         // [16]
     float* part = red + 16;                          // [8][C]
     float acc = 0.f;
-    for (int m = tid; m < a.N; m += NT) {
+    for (int m = tid; m < a.N; m += RB_NT) {
       float dl, l;
       res_head_term(bf2f(a.logits[m]), m, a.N, a.n_real, a.mode, a.loss_scale, dl, l);
       s_dl[m] = dl;
@@ -322,12 +299,12 @@ __global__ __launch_bounds__(512 / TPW * KS) void res8_chain_bwd_kernel(ResBwdAr
     __syncthreads();
     if (tid == 0) {
       float t = 0.f;
-      for (int i = 0; i < NT / 64; i++) t += red[i];
+      for (int i = 0; i < RB_NT / 64; i++) t += red[i];
       a.loss[0] = t;
     }
     if (a.w_grad) {                                  // w_grad[k] += sum_m pooled[m][k] dl[m]: 8 row slices per column, summed in slice order
       const int nsl = 8, per = (a.N + nsl - 1) / nsl;
-      for (int i = tid; i < nsl * RB_C; i += NT) {
+      for (int i = tid; i < nsl * RB_C; i += RB_NT) {
         const int sl = i / RB_C, k = i - sl * RB_C;
         const int m0 = sl * per, m1 = min(a.N, m0 + per);
         float t = 0.f;
@@ -350,23 +327,23 @@ __global__ __launch_bounds__(512 / TPW * KS) void res8_chain_bwd_kernel(ResBwdAr
     }
     return;
   }
-  const int row = (KS == 2 ? 0 : 4 * (wave >> 2)) + (r >> 3), col = r & 7;
+  const int row = (r >> 3), col = r & 7;
   const int b_base = row * RB_RPB + col * RB_PPB + h * 16;
   const int own = (row + 1) * RB_RPB + (col + 1) * RB_PPB + ct * 64 + h * 8;
   const long own_g = (n * 64 + row * 8 + col) * RB_C + ct * 32 + 4 * h;           // the same elements in HBM: + 8 g (+ 32 pixels for tile 1)
   const int wbase = (ct * RB_STEPS + kg * (RB_STEPS / 2)) * 1024;
-  f32x4* part = reinterpret_cast<f32x4*>(smem + RB_LDS) + ct * (TPW * 4 * 64);
+  f32x4* part = reinterpret_cast<f32x4*>(smem + RB_LDS) + ct * (RB_TPW * 4 * 64);
 
-  u32x4 ring[PF];
-  res_ring_fill<PF>(ring, __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(a.wd[0]), 0, RB_WBYTES, 0x00020000), lane * 16, wbase);
-  for (int i = tid; i < RB_LDS / 16; i += NT) reinterpret_cast<u32x4*>(smem)[i] = u32x4{0u, 0u, 0u, 0u};
+  u32x4 ring[RB_PF];
+  res_ring_fill(ring, __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(a.wd[0]), 0, RB_WBYTES, 0x00020000), lane * 16, wbase);
+  for (int i = tid; i < RB_LDS / 16; i += RB_NT) reinterpret_cast<u32x4*>(smem)[i] = u32x4{0u, 0u, 0u, 0u};
   __syncthreads();
   if (a.dpool || a.logits) {                         // gradient of relu + spatial mean: dpool / 64 where y_last > 0
     float dl = 0.f, lterm;
     if (a.logits) res_head_term(bf2f(a.logits[n]), (int)n, a.N, a.n_real, a.mode, a.loss_scale, dl, lterm);
 #pragma unroll
-    for (int it = 0; it < 1024 / NT; it++) {
-      const int q = tid + it * NT, px = q >> 4, c16 = q & 15;
+    for (int it = 0; it < 1024 / RB_NT; it++) {
+      const int q = tid + it * RB_NT, px = q >> 4, c16 = q & 15;
       const bf16x8 yv = *reinterpret_cast<const bf16x8*>(a.ylast + (n * 64 + px) * RB_C + c16 * 8);
       bf16x8 dp;
       if (a.logits) {                                // the head's input gradient, bf16(dl * w) as the head kernel rounds it
@@ -383,7 +360,7 @@ __global__ __launch_bounds__(512 / TPW * KS) void res8_chain_bwd_kernel(ResBwdAr
       if (a.dy_out) *reinterpret_cast<bf16x8*>(a.dy_out + (n * 64 + px) * RB_C + c16 * 8) = o;
     }
   } else {
-    res_load_image<NT>(smem, a.dy + n * 64 * RB_C, tid);
+    res_load_image(smem, a.dy + n * 64 * RB_C, tid);
   }
   __syncthreads();
 
@@ -400,22 +377,22 @@ __global__ __launch_bounds__(512 / TPW * KS) void res8_chain_bwd_kernel(ResBwdAr
     const bool more = b + 1 < a.nblocks;
     const __amdgpu_buffer_rsrc_t r3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(more ? a.wd[2] : wd1), 0, RB_WBYTES, 0x00020000);
 
-    bf16x4 m[TPW][4];
+    bf16x4 m[RB_TPW][4];
     if (kg == 0) {
 #pragma unroll
-    for (int t = 0; t < TPW; t++)
+    for (int t = 0; t < RB_TPW; t++)
 #pragma unroll
       for (int g = 0; g < 4; g++) m[t][g] = *reinterpret_cast<const bf16x4*>(h1 + own_g + t * 32 * RB_C + 8 * g);     // in flight during the conv
     }
-    f32x16 acc[TPW];
+    f32x16 acc[RB_TPW];
 #pragma unroll
-    for (int t = 0; t < TPW; t++)
+    for (int t = 0; t < RB_TPW; t++)
 #pragma unroll
       for (int e = 0; e < 16; e++) acc[t][e] = 0.f;
-    res_conv3x3_ks<false, TPW, PF, KS>(acc, ring, smem, b_base, r2, r1, true, lane * 16, wbase, kg, part, lane);   // input gradient of conv_2
+    res_conv3x3_ks<false>(acc, ring, smem, b_base, r2, r1, true, lane * 16, wbase, kg, part, lane);   // input gradient of conv_2
     if (kg == 0) {
 #pragma unroll
-    for (int t = 0; t < TPW; t++)
+    for (int t = 0; t < RB_TPW; t++)
 #pragma unroll
       for (int g = 0; g < 4; g++) {
         bf16x4 o;
@@ -425,21 +402,21 @@ __global__ __launch_bounds__(512 / TPW * KS) void res8_chain_bwd_kernel(ResBwdAr
       }
     }
     __syncthreads();                                                              // image B = g1 complete
-    if (g1) res_store_image<NT>(smem + RB_IMG, g1 + n * 64 * RB_C, tid);
+    if (g1) res_store_image(smem + RB_IMG, g1 + n * 64 * RB_C, tid);
     if (kg == 0) {
 #pragma unroll
-    for (int t = 0; t < TPW; t++)
+    for (int t = 0; t < RB_TPW; t++)
 #pragma unroll
       for (int g = 0; g < 4; g++) m[t][g] = *reinterpret_cast<const bf16x4*>(xin + own_g + t * 32 * RB_C + 8 * g);
     }
 #pragma unroll
-    for (int t = 0; t < TPW; t++)
+    for (int t = 0; t < RB_TPW; t++)
 #pragma unroll
       for (int e = 0; e < 16; e++) acc[t][e] = 0.f;
-    res_conv3x3_ks<false, TPW, PF, KS>(acc, ring, smem + RB_IMG, b_base, r1, r3, more, lane * 16, wbase, kg, part, lane);   // input gradient of conv_1
+    res_conv3x3_ks<false>(acc, ring, smem + RB_IMG, b_base, r1, r3, more, lane * 16, wbase, kg, part, lane);   // input gradient of conv_1
     if (kg == 0) {
 #pragma unroll
-    for (int t = 0; t < TPW; t++)
+    for (int t = 0; t < RB_TPW; t++)
 #pragma unroll
       for (int g = 0; g < 4; g++) {
         const bf16x4 ds = *reinterpret_cast<const bf16x4*>(smem + own + 4 * t * RB_RPB + 16 * g);    // + dy along the identity shortcut
@@ -450,48 +427,22 @@ __global__ __launch_bounds__(512 / TPW * KS) void res8_chain_bwd_kernel(ResBwdAr
       }
     }
     __syncthreads();                                                              // image A = dx complete
-    if (dx) res_store_image<NT>(smem, dx + n * 64 * RB_C, tid);
+    if (dx) res_store_image(smem, dx + n * 64 * RB_C, tid);
   }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-#ifdef GANK_TUNING
-static int res8_cfg() {          // experiment knob GANK_RES8_CFG = 10*TPW + {1: 8, 2: 12, 3: 24 fragments in flight}; + 100: reduction split over two wave groups
-  static const int v = gank_tune("GANK_RES8_CFG", 122);
-  return v;
-}
-#endif
 constexpr int RB_PART = 4 * 2 * 4 * 64 * 16;      // partial tiles of the K-split form: [4 channel tiles][2 pixel tiles x 4 quads][64 lanes] x 16 B
-template <int TPW, int PF, int KS>
 static int res8_launch_fwd(const ResFwdArgs& a, hipStream_t s) {
-  constexpr int LDS = RB_LDS + (KS == 2 ? RB_PART : 0);
-  GANK_MAX_DYNAMIC_LDS((res8_chain_fwd_kernel<TPW, PF, KS>), LDS, "res8_chain_fwd");
-  hipLaunchKernelGGL((res8_chain_fwd_kernel<TPW, PF, KS>), dim3(a.N), dim3(512 / TPW * KS), LDS, s, a);
+  GANK_MAX_DYNAMIC_LDS(res8_chain_fwd_kernel, RB_LDS + RB_PART, "res8_chain_fwd");
+  hipLaunchKernelGGL(res8_chain_fwd_kernel, dim3(a.N), dim3(RB_NT), RB_LDS + RB_PART, s, a);
   return 0;
 }
-template <int TPW, int PF, int KS>
 static int res8_launch_bwd(const ResBwdArgs& a, hipStream_t s) {
-  constexpr int LDS = RB_LDS + (KS == 2 ? RB_PART : 0);
-  GANK_MAX_DYNAMIC_LDS((res8_chain_bwd_kernel<TPW, PF, KS>), LDS, "res8_chain_bwd");
-  hipLaunchKernelGGL((res8_chain_bwd_kernel<TPW, PF, KS>), dim3(a.N + (a.logits ? 1 : 0)), dim3(512 / TPW * KS), LDS, s, a);
+  GANK_MAX_DYNAMIC_LDS(res8_chain_bwd_kernel, RB_LDS + RB_PART, "res8_chain_bwd");
+  hipLaunchKernelGGL(res8_chain_bwd_kernel, dim3(a.N + (a.logits ? 1 : 0)), dim3(RB_NT), RB_LDS + RB_PART, s, a);
   return 0;
 }
-#ifdef GANK_TUNING
-#define RES8_DISPATCH(fn, a, s)                                      \
-  switch (res8_cfg()) {                                              \
-    case 11: rc = fn<1, 8, 1>(a, s); break;                          \
-    case 12: rc = fn<1, 12, 1>(a, s); break;                         \
-    case 13: rc = fn<1, 24, 1>(a, s); break;                         \
-    case 21: rc = fn<2, 8, 1>(a, s); break;                          \
-    case 22: rc = fn<2, 12, 1>(a, s); break;                         \
-    case 23: rc = fn<2, 24, 1>(a, s); break;                         \
-    case 121: rc = fn<2, 6, 2>(a, s); break;                         \
-    case 123: rc = fn<2, 18, 2>(a, s); break;                        \
-    default: rc = fn<2, 12, 2>(a, s); break;                         \
-  }
-#else          // (4 channel tiles) x (2 halves of the reduction), two pixel tiles per wave, 12 weight fragments in flight
-#define RES8_DISPATCH(fn, a, s) rc = fn<2, 12, 2>(a, s)
-#endif
 
 extern "C" int gank_res8_chain_fwd_head(const void* x, const void* const* w_rfrag, const float* const* bias, void* const* h1,
                                         void* const* y, void* pooled, const float* head_w, const float* head_b, void* logits, int N, int C,
@@ -515,8 +466,7 @@ extern "C" int gank_res8_chain_fwd_head(const void* x, const void* const* w_rfra
   gank_prof_begin(0, 2.0 * nblocks * 2.0 * N * 64.0 * RB_C * 9.0 * RB_C, s,
                   2.0 * N * 64.0 * RB_C * (1 + 2 * nblocks) + 2.0 * nblocks * RB_WBYTES);
   gank_prof_tag(0, "res8_chain_fwd_kernel");
-  int rc = 0;
-  RES8_DISPATCH(res8_launch_fwd, a, s);
+  const int rc = res8_launch_fwd(a, s);
   gank_prof_end(0, s);
   if (rc) return rc;
   GANK_LAUNCH_OK("res8_chain_fwd");
@@ -561,8 +511,7 @@ static int res8_chain_bwd_impl(const void* dy, const void* dpool, const void* yl
   gank_prof_begin(0, 2.0 * nblocks * 2.0 * N * 64.0 * RB_C * 9.0 * RB_C, s,
                   2.0 * N * 64.0 * RB_C * (1 + 4 * nblocks) + 2.0 * nblocks * RB_WBYTES);
   gank_prof_tag(0, "res8_chain_bwd_kernel");
-  int rc = 0;
-  RES8_DISPATCH(res8_launch_bwd, a, s);
+  const int rc = res8_launch_bwd(a, s);
   gank_prof_end(0, s);
   if (rc) return rc;
   GANK_LAUNCH_OK("res8_chain_bwd");
@@ -613,8 +562,7 @@ struct CpFwdArgs {
   const bf16* res;        // optional residual at pooled resolution [N,Hp,Wp,Cout]
   bf16* y;                // [N,Hp,Wp,Cout]
   int N, Hp, Wp, Cin, Cout, relu;
-  int xcd;                // XCD-aware block order (resident_xcd_env): workgroups that share an input patch share an L2
-  int dbg;                // TUNING builds (GANK_CPOOL_DBG, timing only): 1 = input loads out of range (zero fill, no traffic), 2 = no output
+  int xcd;                // XCD-aware block order: workgroups that share an input patch share an L2
 };
 
 struct CpBwdArgs {
@@ -628,8 +576,9 @@ struct CpBwdArgs {
 }  // namespace
 
 // fprop: 8 waves = (Cout tile ct = wave & 3) x (pixel group pg = wave >> 2); a workgroup covers 128 output channels
-template <int PW, int TPW, int PF, int NTAP = 16>      // NTAP != 16: timing experiments only (GANK_CPOOL_TAPS, tuning builds)
+template <int PW, int TPW>
 __global__ __launch_bounds__(512) void cpool_res_fprop_kernel(CpFwdArgs a) {
+  constexpr int PF = 8, NTAP = 16;                   // weight fragments in flight per wave; taps of the 4x4 stride-2 form
   using G = CpGeom<PW>;
   constexpr int NSTEP = NTAP * 4;
   static_assert(2 * TPW * G::TROWS == G::PHH, "8 waves = 4 channel tiles x 2 pixel groups must tile the patch");
@@ -682,9 +631,6 @@ __global__ __launch_bounds__(512) void cpool_res_fprop_kernel(CpFwdArgs a) {
     const int iy = 2 * py0 - 1 + hr, ix = 2 * px0 - 1 + hc;
     const bool ok = on && (unsigned)iy < (unsigned)H2 && (unsigned)ix < (unsigned)W2;
     p_off[j] = ok ? (((n * H2 + iy) * W2 + ix) * a.Cin + c16 * 8) * 2 : OOB;
-#ifdef GANK_TUNING
-    if (a.dbg & 1) p_off[j] = OOB;
-#endif
     p_lds[j] = on ? ((hr & 1) * 2 + (hc & 1)) * G::PLANE + (hr >> 1) * G::RP + (hc >> 1) * CP_PP + c16 * 16 : -1;
   }
   u32x4 rP[NLD];
@@ -736,9 +682,6 @@ __global__ __launch_bounds__(512) void cpool_res_fprop_kernel(CpFwdArgs a) {
   }
 
   // epilogue: after acc_widen the lane holds channels 16q + 8h .. +7 of one pooled pixel: 16-byte pieces
-#ifdef GANK_TUNING
-  if (a.dbg & 2) return;
-#endif
 #pragma unroll
   for (int t = 0; t < TPW; t++) {
     const int py = py0 + (pg * TPW + t) * G::TROWS + trow, px = px0 + tcol;
@@ -773,8 +716,12 @@ __global__ __launch_bounds__(512) void cpool_res_fprop_kernel(CpFwdArgs a) {
 // the one-group form was each CU streaming the whole 16 * Cin * 128 * 2-byte operand through its L1 (1 MB at 40-70 GB/s);
 // here a CU streams half of it and a wave a quarter; the next round's input pieces are requested before the current round's
 // MFMAs (in flight behind the weight stream instead of in front of it).
-template <int PF, int NTAP = 16>                       // NTAP != 16: timing experiments only
+// PF = weight fragments in flight per wave: every launch uses 8.  The kernel stays a template on purpose: as a plain function it is
+// emitted ahead of the instantiations and moves every kernel behind it in the code object; the training step was measured with this
+// layout (profiles/knob_retirement.txt).
+template <int PF>
 __global__ __launch_bounds__(512) void cpool_res_fprop_k2_kernel(CpFwdArgs a) {
+  constexpr int NTAP = 16;                           // taps of the 4x4 stride-2 form
   using G = CpGeom<8>;
   constexpr int PW = 8, NSTEP = NTAP * 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];          // [2 K groups][IMG]
@@ -920,123 +867,13 @@ template <int PW> struct CdGeom {
 };
 }  // namespace
 
-template <int PW, int TPW, int PF>
-__global__ __launch_bounds__(512) void cpool_res_dgrad_kernel(CpBwdArgs a) {
-  using G = CdGeom<PW>;
-  static_assert(2 * TPW * G::TROWS == G::PHH, "8 waves = 4 channel tiles x 2 pixel groups must tile the patch");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ct = wave & 3, pg = wave >> 2;
-  const int r = lane & 31, h = lane >> 5;
-  const int pw_n = a.Wp / PW, ph_n = a.Hp / G::PHH, cgroups = a.Cin >> 7;
-  int bid = a.xcd ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
-  const int cg = bid % cgroups; bid /= cgroups;
-  const int n = bid / (pw_n * ph_n), pr = bid - n * pw_n * ph_n;
-  const int py0 = (pr / pw_n) * G::PHH, px0 = (pr % pw_n) * PW;
-  const int trow = PW == 16 ? (r >> 4) : (r >> 3), tcol = PW == 16 ? (r & 15) : (r & 7);
-  const int b_base = (pg * TPW * G::TROWS + trow) * G::RP + tcol * G::PP + h * 16;      // halo pixel (row, col): dy pixel (py0-1+row, px0-1+col)
-
-  // operand: [phase][Cin/32][4 taps][Cout/16 kk][64][8]; Cout == 128 -> 32 steps of 1 KB per (phase, tile)
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(a.w), 0, 4 * a.Cin * 4 * a.Cout * 2, 0x00020000);
-  const int tiles = a.Cin >> 5, tile = cg * 4 + ct;
-  auto wofs = [&](int phase, int s) { return ((phase * tiles + tile) * 32 + s) * 1024; };
-  u32x4 ring[PF];
-  static_assert(32 % PF == 0, "ring position is phase-invariant");
-#pragma unroll
-  for (int s = 0; s < PF; s++) ring[s] = __builtin_amdgcn_raw_buffer_load_b128(rw, lane * 16, wofs(0, s), 0);
-
-  // stage the dy halo: (PHH + 2) x (PW + 2) pixels x 16 pieces
-  constexpr int HR = G::PHH + 2, HC = PW + 2, NPIECE = HR * HC * 16;
-  constexpr int NLD = (NPIECE + 511) / 512;
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(a.dy), 0, a.N * a.Hp * a.Wp * a.Cout * 2, 0x00020000);
-  constexpr int OOB = 0x7FFFFFF0;
-#pragma unroll
-  for (int j = 0; j < NLD; j++) {
-    const int q = tid + j * 512;
-    if (NPIECE % 512 == 0 || q < NPIECE) {
-      const int hp = q >> 4, c16 = q & 15;
-      const int hr = hp / HC, hc = hp - hr * HC;
-      const int iy = py0 - 1 + hr, ix = px0 - 1 + hc;
-      const bool ok = (unsigned)iy < (unsigned)a.Hp && (unsigned)ix < (unsigned)a.Wp;
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(ry, ok ? (((n * a.Hp + iy) * a.Wp + ix) * a.Cout + c16 * 8) * 2 : OOB, 0, 0);
-      *reinterpret_cast<u32x4*>(smem + hr * G::RP + hc * G::PP + c16 * 16) = v;
-    }
-  }
-  __syncthreads();
-
-  const int H2 = 2 * a.Hp, W2 = 2 * a.Wp;
-#pragma unroll 1
-  for (int phase = 0; phase < 4; phase++) {
-    const int pa = phase >> 1, pb = phase & 1;
-    const int poff = pa * G::RP + pb * G::PP;                  // tap (i, j) reads halo pixel (y + i + pa, x + j + pb)
-    f32x16 acc[TPW];
-#pragma unroll
-    for (int t = 0; t < TPW; t++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) acc[t][e] = 0.f;
-    // relu masks of this phase's outputs: requested now, consumed after the K loop
-    bf16x8 mk[TPW][2];
-    if (a.mask) {
-#pragma unroll
-      for (int t = 0; t < TPW; t++) {
-        const int y = py0 + (pg * TPW + t) * G::TROWS + trow, x = px0 + tcol;
-        const long m = ((long)n * H2 + 2 * y + pa) * W2 + 2 * x + pb;
-#pragma unroll
-        for (int q = 0; q < 2; q++) mk[t][q] = *reinterpret_cast<const bf16x8*>(a.mask + m * a.Cin + cg * 128 + ct * 32 + 16 * q + 8 * h);
-      }
-    }
-    constexpr int PB = 2;
-    bf16x8 bq[PB + 1][TPW];
-    auto read_b = [&](int s, bf16x8 (&dst)[TPW]) {
-      const int tap = s >> 3, kk = s & 7, ti = tap >> 1, tj = tap & 1;
-#pragma unroll
-      for (int t = 0; t < TPW; t++)
-        dst[t] = *reinterpret_cast<const bf16x8*>(smem + b_base + poff + (t * G::TROWS + ti) * G::RP + tj * G::PP + kk * 32);
-    };
-#pragma unroll
-    for (int s = 0; s < PB; s++) read_b(s, bq[s]);
-#pragma unroll
-    for (int s = 0; s < 32; s++) {
-      if (s + PB < 32) read_b(s + PB, bq[(s + PB) % (PB + 1)]);
-      const bf16x8 fa = __builtin_bit_cast(bf16x8, ring[s % PF]);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int t = 0; t < TPW; t++) acc[t] = GANK_MFMA32(fa, bq[s % (PB + 1)][t], acc[t]);
-      __builtin_amdgcn_sched_barrier(0);
-      {
-        const int nx = s + PF;
-        const int np = nx < 32 ? phase : (phase < 3 ? phase + 1 : 3), ns = nx < 32 ? nx : (phase < 3 ? nx - 32 : 31);
-        ring[s % PF] = __builtin_amdgcn_raw_buffer_load_b128(rw, lane * 16, wofs(np, ns), 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int t = 0; t < TPW; t++) {
-      const int y = py0 + (pg * TPW + t) * G::TROWS + trow, x = px0 + tcol;
-      const long m = ((long)n * H2 + 2 * y + pa) * W2 + 2 * x + pb;
-#pragma unroll
-      for (int q = 0; q < 2; q++) {
-        const int ci = cg * 128 + ct * 32 + 16 * q + 8 * h;
-        float v[8];
-        acc_widen(acc[t], q, 1.0f, v);
-        if (a.mask) {
-#pragma unroll
-          for (int e = 0; e < 8; e++) v[e] = bf2f(mk[t][q][e]) > 0.f ? v[e] : 0.f;
-        }
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; e++) o[e] = f2bf(v[e]);
-        *reinterpret_cast<bf16x8*>(a.dx + m * a.Cin + ci) = o;
-      }
-    }
-  }
-}
-
-// The same with the 8 waves as (4 channel tiles) x (2 halves of each phase's reduction) instead of x (2 pixel groups): a wave
+// The 8 waves are (4 channel tiles) x (2 halves of each phase's reduction), not x (2 pixel groups): a wave
 // owns ALL pixel tiles of the patch, so every weight fragment is requested by one wave of the workgroup (and feeds TW MFMAs)
 // instead of by two -- the CU's L1 path, which bounds these kernels, carries half the bytes.  After a phase's K loop the two
 // halves swap partial tiles through LDS: group kg finishes (masks, rounds, stores) the tiles t with t / (TW/2) == kg.
+// PF = weight fragments in flight per wave: every launch uses 8.  PF = 16 lost its A/B run and is reached by no launch; it is still
+// instantiated at the end of this file because the surviving kernels ran 0.1 - 0.2 % of the training step slower without the retired
+// ones in the code object (profiles/knob_retirement.txt).
 template <int PW, int PF>
 __global__ __launch_bounds__(512) void cpool_res_dgrad_ks_kernel(CpBwdArgs a) {
   using G = CdGeom<PW>;
@@ -1208,7 +1045,6 @@ struct CpBwdWgArgs {
   float* slabs;           // null: fp32 atomics into the four targets; else [grid][32][128] plain stores (Cin == 128), summed by the caller
   int N, Hp, Wp, Cin, Cout;
   int xcd;
-  int dbg;                // TUNING builds (GANK_IMGWG_DBG): 1 = no final atomics, 2 = no filter-gradient section, 4 = no Xcol build
 };
 constexpr int WG_XI_PITCH = 112;                       // image row in LDS (bf16): 8 zeros, 96 values, 8 zeros
 constexpr int WG_XI = CdGeom<16>::IMG + 2 * 4 * 2 * 4 * 64 * 16;     // byte offsets behind the halo image and the partial-tile area
@@ -1222,6 +1058,9 @@ __device__ __forceinline__ s16x4 res_tr_read(const char* p) {
 }
 }  // namespace
 
+// PF = weight fragments in flight per wave: every launch uses 8.  The kernel stays a template on purpose: as a plain function it is
+// emitted ahead of the instantiations and moves every kernel behind it in the code object; the training step was measured with this
+// layout (profiles/knob_retirement.txt).
 template <int PF>
 __global__ __launch_bounds__(512) void cpool_res_dgrad_imgwg_kernel(CpBwdWgArgs a) {
   constexpr int PW = 16;
@@ -1390,9 +1229,6 @@ __global__ __launch_bounds__(512) void cpool_res_dgrad_imgwg_kernel(CpBwdWgArgs 
     if (kg == 0) body(std::integral_constant<int, 0>{});
     else body(std::integral_constant<int, 1>{});
     if (phase > 0) __syncthreads();                    // the previous phase's partials have been read; every wave has left phase - 1
-#ifdef GANK_TUNING
-    if (!(a.dbg & 4))
-#endif
     if (phase < 3) build_xcol(phase + 1);              // (its buffer was last read in phase - 1; visible after this phase's barrier below)
     auto finish = [&](auto group) {
       constexpr int KG = decltype(group)::value;
@@ -1425,9 +1261,6 @@ __global__ __launch_bounds__(512) void cpool_res_dgrad_imgwg_kernel(CpBwdWgArgs 
           for (int e = 0; e < 8; e++) o[e] = f2bf(v[e]);
           *reinterpret_cast<bf16x8*>(dh + r * 64 + 32 * q + 16 * h) = o;
         }
-#ifdef GANK_TUNING
-        if (a.dbg & 2) continue;
-#endif
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the wave's own writes: program order + this wait, no barrier
         const char* xc = smem + WG_XCOL + (phase & 1) * 8192 + (KG * TH + t) * 32 * 64 + tr64;
 #pragma unroll
@@ -1447,9 +1280,6 @@ __global__ __launch_bounds__(512) void cpool_res_dgrad_imgwg_kernel(CpBwdWgArgs 
 
   // ---- the two K groups of a channel tile meet in LDS (each keeps one half of the rows), then one [32][32] tile per wave pair
   // leaves as fp32 atomics: rows 0..26 -> dw1, 27 -> db1, 28..30 -> dws, 31 -> dbs
-#ifdef GANK_TUNING
-  if (a.dbg & 1) { if (accw[0] == 123.456f) a.dw1[0] = 1.f; return; }
-#endif
   __syncthreads();
   float* ex = reinterpret_cast<float*>(smem + G::IMG) + ((kg * 4 + ct) * 8) * 64;
   const float* ex_in = reinterpret_cast<const float*>(smem + G::IMG) + (((kg ^ 1) * 4 + ct) * 8) * 64;
@@ -1475,10 +1305,6 @@ __global__ __launch_bounds__(512) void cpool_res_dgrad_imgwg_kernel(CpBwdWgArgs 
     float* dst = nullptr;
     if (k < 27) {
       dst = a.dw1 + (long)k * a.Cin + cg * 128 + col;
-#ifdef GANK_TUNING          // contention experiments: one copy of the tile per XCD (8) / per workgroup (16); the caller's buffer is that large
-      if (a.dbg & 8) dst += (blockIdx.x & 7) * 8192;
-      if (a.dbg & 16) dst += blockIdx.x * 8192;
-#endif
     } else if (k == 27) dst = a.db1 ? a.db1 + cg * 128 + col : nullptr;
     else if (k < 31) dst = (shortcut && a.dws) ? a.dws + (long)(k - 28) * a.Cout + col : nullptr;
     else dst = (shortcut && a.dbs) ? a.dbs + col : nullptr;
@@ -1486,15 +1312,7 @@ __global__ __launch_bounds__(512) void cpool_res_dgrad_imgwg_kernel(CpBwdWgArgs 
   }
 }
 
-static int resident_xcd_env() {
-  static const int v = gank_tune("GANK_RESIDENT_XCD", 1);   // experiment knob: 0 = hardware block order (neighbouring ids round-robin over the XCDs)
-  return v;
-}
 static bool cpool_res_geom_ok(int Hp, int Wp) { return Hp % 8 == 0 && (Wp % 16 == 0 || Wp == 8); }
-static int cpool_k2_env() {
-  static const int v = gank_tune("GANK_CPOOL_K2", 1);   // experiment knob: GANK_CPOOL_K2=0 keeps the one-group kernel for 8-wide patches
-  return v;
-}
 
 extern "C" int gank_cpool_res_fprop(const void* x, const void* w_rfrag, const float* bias, const void* residual, void* y, int N, int Hp,
                                     int Wp, int Cin, int Cout, int flags, void* stream) {
@@ -1505,31 +1323,16 @@ extern "C" int gank_cpool_res_fprop(const void* x, const void* w_rfrag, const fl
   CpFwdArgs a{};
   a.x = (const bf16*)x; a.w = (const bf16*)w_rfrag; a.bias = bias; a.res = (const bf16*)residual; a.y = (bf16*)y;
   a.N = N; a.Hp = Hp; a.Wp = Wp; a.Cin = Cin; a.Cout = Cout; a.relu = (flags & GANK_IN_RELU) ? 1 : 0;
-  a.xcd = resident_xcd_env();
-#ifdef GANK_TUNING
-  a.dbg = gank_tune("GANK_CPOOL_DBG", 0);
-#endif
+  a.xcd = 1;
   hipStream_t s = (hipStream_t)stream;
   const double M = (double)N * Hp * Wp;
   gank_prof_begin(0, 2.0 * M * Cout * 16.0 * Cin, s, 2.0 * (4.0 * M * Cin + 16.0 * Cin * Cout + M * Cout + (residual ? M * Cout : 0.0)));
-#ifdef GANK_TUNING
-  static const int taps_env = gank_tune("GANK_CPOOL_TAPS", 16);   // timing only: 9 = the step count of a box-filter + 3x3 stride-2 form (results are wrong)
-  if (taps_env == 9 && Wp % 16 == 0) {
-    const int grid = N * (Hp / 8) * (Wp / 16) * (Cout / 128);
-    GANK_MAX_DYNAMIC_LDS((cpool_res_fprop_kernel<16, 2, 12, 9>), CpGeom<16>::IMG, "cpool_res_fprop");
-    hipLaunchKernelGGL((cpool_res_fprop_kernel<16, 2, 12, 9>), dim3(grid), dim3(512), CpGeom<16>::IMG, s, a);
-  } else if (taps_env == 9 && Cin % 128 == 0 && N * (Hp / 8) * (Cout / 128) < 256) {
-    const int grid = N * (Hp / 8) * (Cout / 64);
-    GANK_MAX_DYNAMIC_LDS((cpool_res_fprop_k2_kernel<12, 9>), 2 * CpGeom<8>::IMG, "cpool_res_fprop");
-    hipLaunchKernelGGL((cpool_res_fprop_k2_kernel<12, 9>), dim3(grid), dim3(512), 2 * CpGeom<8>::IMG, s, a);
-  } else
-#endif
   if (Wp % 16 == 0) {
     const int grid = N * (Hp / 8) * (Wp / 16) * (Cout / 128);
-    GANK_MAX_DYNAMIC_LDS((cpool_res_fprop_kernel<16, 2, 8>), CpGeom<16>::IMG, "cpool_res_fprop");
-    gank_prof_tag(0, "cpool_res_fprop_kernel<16, 2, 8>");
-    hipLaunchKernelGGL((cpool_res_fprop_kernel<16, 2, 8>), dim3(grid), dim3(512), CpGeom<16>::IMG, s, a);
-  } else if (Cin % 128 == 0 && cpool_k2_env() && N * (Hp / 8) * (Cout / 128) < 256) {
+    GANK_MAX_DYNAMIC_LDS((cpool_res_fprop_kernel<16, 2>), CpGeom<16>::IMG, "cpool_res_fprop");
+    gank_prof_tag(0, "cpool_res_fprop_kernel<16, 2>");
+    hipLaunchKernelGGL((cpool_res_fprop_kernel<16, 2>), dim3(grid), dim3(512), CpGeom<16>::IMG, s, a);
+  } else if (Cin % 128 == 0 && N * (Hp / 8) * (Cout / 128) < 256) {
     // fewer one-per-CU workgroups than CUs: 64 output channels per workgroup, the reduction split over two wave groups
     const int grid = N * (Hp / 8) * (Cout / 64);
     GANK_MAX_DYNAMIC_LDS((cpool_res_fprop_k2_kernel<8>), 2 * CpGeom<8>::IMG, "cpool_res_fprop");
@@ -1537,9 +1340,9 @@ extern "C" int gank_cpool_res_fprop(const void* x, const void* w_rfrag, const fl
     hipLaunchKernelGGL((cpool_res_fprop_k2_kernel<8>), dim3(grid), dim3(512), 2 * CpGeom<8>::IMG, s, a);
   } else {
     const int grid = N * (Hp / 8) * (Cout / 128);
-    GANK_MAX_DYNAMIC_LDS((cpool_res_fprop_kernel<8, 1, 8>), CpGeom<8>::IMG, "cpool_res_fprop");
-    gank_prof_tag(0, "cpool_res_fprop_kernel<8, 1, 8>");
-    hipLaunchKernelGGL((cpool_res_fprop_kernel<8, 1, 8>), dim3(grid), dim3(512), CpGeom<8>::IMG, s, a);
+    GANK_MAX_DYNAMIC_LDS((cpool_res_fprop_kernel<8, 1>), CpGeom<8>::IMG, "cpool_res_fprop");
+    gank_prof_tag(0, "cpool_res_fprop_kernel<8, 1>");
+    hipLaunchKernelGGL((cpool_res_fprop_kernel<8, 1>), dim3(grid), dim3(512), CpGeom<8>::IMG, s, a);
   }
   gank_prof_end(0, s);
   GANK_LAUNCH_OK("cpool_res_fprop");
@@ -1555,45 +1358,23 @@ extern "C" int gank_cpool_res_dgrad(const void* dy, const void* w_rfrag, const v
   CpBwdArgs a{};
   a.dy = (const bf16*)dy; a.w = (const bf16*)w_rfrag; a.mask = (const bf16*)relu_ref; a.dx = (bf16*)dx;
   a.N = N; a.Hp = Hp; a.Wp = Wp; a.Cin = Cin; a.Cout = Cout;
-  a.xcd = resident_xcd_env();
+  a.xcd = 1;
   hipStream_t s = (hipStream_t)stream;
   const double M = (double)N * Hp * Wp;
   gank_prof_begin(0, 2.0 * M * 4.0 * Cin * 4.0 * Cout, s, 2.0 * (M * Cout + 16.0 * Cin * Cout + 4.0 * M * Cin + (relu_ref ? 4.0 * M * Cin : 0.0)));
-  static const int ks_env = gank_tune("GANK_CPOOL_DGRAD_KS", 1);   // experiment knob: 0 keeps the (channel tile) x (pixel group) wave layout
+  // (channel tile) x (half of the reduction) wave layout; partial tiles behind the image: [2 groups][4 channel tiles][tiles x 4 quads][64 lanes] x 16 B
   if (Wp % 16 == 0) {
     const int grid = N * (Hp / 8) * (Wp / 16) * (Cin / 128);
-    if (ks_env == 2) {
-      constexpr int LDS = CdGeom<16>::IMG + 2 * 4 * 2 * 4 * 64 * 16;
-      GANK_MAX_DYNAMIC_LDS((cpool_res_dgrad_ks_kernel<16, 16>), LDS, "cpool_res_dgrad");
-      gank_prof_tag(0, "cpool_res_dgrad_ks_kernel<16, 16>");
-      hipLaunchKernelGGL((cpool_res_dgrad_ks_kernel<16, 16>), dim3(grid), dim3(512), LDS, s, a);
-    } else if (ks_env) {
-      constexpr int LDS = CdGeom<16>::IMG + 2 * 4 * 2 * 4 * 64 * 16;      // + [2 groups][4 channel tiles][2 tiles x 4 quads][64 lanes] x 16 B
-      GANK_MAX_DYNAMIC_LDS((cpool_res_dgrad_ks_kernel<16, 8>), LDS, "cpool_res_dgrad");
-      gank_prof_tag(0, "cpool_res_dgrad_ks_kernel<16, 8>");
-      hipLaunchKernelGGL((cpool_res_dgrad_ks_kernel<16, 8>), dim3(grid), dim3(512), LDS, s, a);
-    } else {
-      GANK_MAX_DYNAMIC_LDS((cpool_res_dgrad_kernel<16, 2, 8>), CdGeom<16>::IMG, "cpool_res_dgrad");
-      gank_prof_tag(0, "cpool_res_dgrad_kernel<16, 2, 8>");
-      hipLaunchKernelGGL((cpool_res_dgrad_kernel<16, 2, 8>), dim3(grid), dim3(512), CdGeom<16>::IMG, s, a);
-    }
+    constexpr int LDS = CdGeom<16>::IMG + 2 * 4 * 2 * 4 * 64 * 16;
+    GANK_MAX_DYNAMIC_LDS((cpool_res_dgrad_ks_kernel<16, 8>), LDS, "cpool_res_dgrad");
+    gank_prof_tag(0, "cpool_res_dgrad_ks_kernel<16, 8>");
+    hipLaunchKernelGGL((cpool_res_dgrad_ks_kernel<16, 8>), dim3(grid), dim3(512), LDS, s, a);
   } else {
     const int grid = N * (Hp / 8) * (Cin / 128);
-    if (ks_env == 2) {
-      constexpr int LDS = CdGeom<8>::IMG + 2 * 4 * 1 * 4 * 64 * 16;
-      GANK_MAX_DYNAMIC_LDS((cpool_res_dgrad_ks_kernel<8, 16>), LDS, "cpool_res_dgrad");
-      gank_prof_tag(0, "cpool_res_dgrad_ks_kernel<8, 16>");
-      hipLaunchKernelGGL((cpool_res_dgrad_ks_kernel<8, 16>), dim3(grid), dim3(512), LDS, s, a);
-    } else if (ks_env) {
-      constexpr int LDS = CdGeom<8>::IMG + 2 * 4 * 1 * 4 * 64 * 16;
-      GANK_MAX_DYNAMIC_LDS((cpool_res_dgrad_ks_kernel<8, 8>), LDS, "cpool_res_dgrad");
-      gank_prof_tag(0, "cpool_res_dgrad_ks_kernel<8, 8>");
-      hipLaunchKernelGGL((cpool_res_dgrad_ks_kernel<8, 8>), dim3(grid), dim3(512), LDS, s, a);
-    } else {
-      GANK_MAX_DYNAMIC_LDS((cpool_res_dgrad_kernel<8, 1, 8>), CdGeom<8>::IMG, "cpool_res_dgrad");
-      gank_prof_tag(0, "cpool_res_dgrad_kernel<8, 1, 8>");
-      hipLaunchKernelGGL((cpool_res_dgrad_kernel<8, 1, 8>), dim3(grid), dim3(512), CdGeom<8>::IMG, s, a);
-    }
+    constexpr int LDS = CdGeom<8>::IMG + 2 * 4 * 1 * 4 * 64 * 16;
+    GANK_MAX_DYNAMIC_LDS((cpool_res_dgrad_ks_kernel<8, 8>), LDS, "cpool_res_dgrad");
+    gank_prof_tag(0, "cpool_res_dgrad_ks_kernel<8, 8>");
+    hipLaunchKernelGGL((cpool_res_dgrad_ks_kernel<8, 8>), dim3(grid), dim3(512), LDS, s, a);
   }
   gank_prof_end(0, s);
   GANK_LAUNCH_OK("cpool_res_dgrad");
@@ -1615,9 +1396,7 @@ extern "C" int gank_cpool_res_dgrad_image_wgrad(const void* dy, const void* w_rf
   GANK_REQUIRE(!slabs || Cin == 128, "cpool_res_dgrad_image_wgrad: the slab form takes Cin == 128 (got %d)", Cin);
   a.xpool = (const bf16*)x_pooled; a.dw1 = dw1; a.db1 = db1; a.dws = dws; a.dbs = dbs; a.slabs = slabs;
   a.N = N; a.Hp = Hp; a.Wp = Wp; a.Cin = Cin; a.Cout = Cout;
-  a.xcd = resident_xcd_env();
-  static const int dbg = gank_tune("GANK_IMGWG_DBG", 0);
-  a.dbg = dbg;
+  a.xcd = 1;
   hipStream_t s = (hipStream_t)stream;
   const double M = (double)N * Hp * Wp;
   // the input gradient's multiply-adds + the two filter gradients'; bytes: dy, the operand, the relu reference, the images (no dx)
@@ -1684,10 +1463,10 @@ struct I16Args {
 // the reduction: K-steps 0,1 / 2,3 of every tap), 4 pixel tiles each, so every weight fragment is still requested once per
 // workgroup and feeds 4 MFMAs; the two partial sums of a tile meet through LDS after the last chunk and each wave of a pair
 // finishes two of the four tiles.
-template <int PF, int TW, bool HALF = false, bool NORM = false>
-__global__ __launch_bounds__(HALF ? 512 : 2048 / TW) void img16_conv3x3_kernel(I16Args a) {
-  static_assert(!HALF || TW == 4, "half-image form: 4 pixel tiles per wave");
-  constexpr int NT = HALF ? 512 : 2048 / TW;
+template <int PF, bool HALF = false, bool NORM = false>
+__global__ __launch_bounds__(512) void img16_conv3x3_kernel(I16Args a) {
+  constexpr int TW = 4;                              // pixel tiles per wave
+  constexpr int NT = 512;
   constexpr int HROWS = HALF ? 10 : 18, IMG = HROWS * I16_RP;            // resident halo rows, bytes per chunk image
   constexpr int STEPS = HALF ? 18 : 36, KPT = HALF ? 2 : 4;              // K-steps of a chunk this wave executes; per tap
   extern __shared__ __attribute__((aligned(16))) char smem[];          // [2][IMG] (HALF: at least the 64-KB exchange area)
@@ -1697,7 +1476,7 @@ __global__ __launch_bounds__(HALF ? 512 : 2048 / TW) void img16_conv3x3_kernel(I
   }
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ct = wave & 3, pg = (HALF || TW == 8) ? 0 : wave >> 2, kh = HALF ? wave >> 2 : 0;
+  const int ct = wave & 3, pg = HALF ? 0 : wave >> 2, kh = HALF ? wave >> 2 : 0;
   const int r = lane & 31, h = lane >> 5;
   const int cgroups = a.Cout >> 7;
   const int lid = a.xcd ? xcd_remap(blockIdx.x, a.lb.blocks > 0 ? a.main_blocks : (int)gridDim.x) : blockIdx.x;
@@ -1940,9 +1719,6 @@ __global__ __launch_bounds__(HALF ? 512 : 2048 / TW) void img16_conv3x3_kernel(I
       tsum += (t4[0] + t4[1]) + (t4[2] + t4[3]);
     }
     float* dst = a.stat_sums + ((long)(n / a.stat_n_per_group) * GANK_STAT_SLOTS + (blockIdx.x % GANK_STAT_SLOTS)) * 2 * a.Cout;
-#ifdef GANK_TUNING
-    if (gank_stats_dbg) return;
-#endif
     atomicAdd(dst + st * a.Cout + cg * 128 + ct * 32 + cw, tsum);
   }
 }
@@ -2018,72 +1794,44 @@ static int img16_conv3x3_impl(const void* x, const void* w_rfrag, const float* b
   a.x = (const bf16*)x; a.w = (const bf16*)w_rfrag; a.bias = bias; a.mask = (const bf16*)relu_ref; a.res = (const bf16*)residual; a.y = (bf16*)y;
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.relu = (flags & GANK_IN_RELU) ? 1 : 0;
   a.res_up = (flags & GANK_RES_UPSAMPLE2X) ? 1 : 0; a.stat_sums = stat_sums; a.stat_n_per_group = stat_sums ? N / stat_groups : 1;
-  a.xcd = resident_xcd_env();
+  a.xcd = 1;
   a.bias_labels = bias_labels; a.bias_V = bias_V;
   if (lb) a.lb = *lb;
   a.res_pitch = res_pitch; a.res_scale = res_scale;
-  const bool half_form = !cbn && (gank_tune("GANK_IMG16_HALF", 1) == 2 || (gank_tune("GANK_IMG16_HALF", 1) == 1 && N * (Cout / 128) < 256));
+  const bool half_form = !cbn && N * (Cout / 128) < 256;   // half images when the whole-image grid leaves CUs idle
   a.main_blocks = (half_form ? 2 : 1) * N * (Cout / 128);
   if (cbn) {
     a.cbn_labels = cbn->labels; a.cbn_gamma = cbn->gamma; a.cbn_beta = cbn->beta; a.cbn_stats = cbn->stats;
     a.cbn_n_per_group = N / cbn->groups; a.cbn_n_labels = cbn->n_labels;
   }
   hipStream_t s = (hipStream_t)stream;
-  if (stat_sums) gank_stats_dbg_init();
   if (stat_sums && !(flags & GANK_STATS_PREZEROED)) {
     const int nz = stat_groups * GANK_STAT_SLOTS * 2 * Cout;
     hipLaunchKernelGGL(i16_zero_kernel, dim3((nz + 255) / 256), dim3(256), 0, s, stat_sums, nz);
   }
   const double M = (double)N * 256;
   gank_prof_begin(0, 2.0 * M * Cout * 9.0 * Cin, s, 2.0 * (M * Cin + 9.0 * Cin * Cout + M * Cout * (1 + (relu_ref ? 1 : 0) + (residual ? 1 : 0))));
-  static const int cfg_env = gank_tune("GANK_IMG16_CFG", 412);   // experiment knob: 100 * (pixel tiles per wave) + weight fragments in flight
-  static const int half_env = gank_tune("GANK_IMG16_HALF", 1);   // experiment knob: 0 = whole images only, 1 = half images when the whole-image grid leaves CUs idle, 2 = always
   if (cbn) {          // whole-image form only (the passes this serves have N * Cout / 128 >= 256 workgroups)
-    gank_prof_tag(0, "img16_conv3x3_kernel<12, 4, false, true>");
-    GANK_MAX_DYNAMIC_LDS((img16_conv3x3_kernel<12, 4, false, true>), 2 * I16_IMG, "cbn_relu_img16_conv3x3");
-    hipLaunchKernelGGL((img16_conv3x3_kernel<12, 4, false, true>), dim3(a.main_blocks + a.lb.blocks), dim3(512), 2 * I16_IMG, s, a);
+    gank_prof_tag(0, "img16_conv3x3_kernel<12, false, true>");
+    GANK_MAX_DYNAMIC_LDS((img16_conv3x3_kernel<12, false, true>), 2 * I16_IMG, "cbn_relu_img16_conv3x3");
+    hipLaunchKernelGGL((img16_conv3x3_kernel<12, false, true>), dim3(a.main_blocks + a.lb.blocks), dim3(512), 2 * I16_IMG, s, a);
     gank_prof_end(0, s);
     GANK_LAUNCH_OK("cbn_relu_img16_conv3x3");
     return 0;
   }
-  if (half_env == 2 || (half_env == 1 && N * (Cout / 128) < 256)) {
+  if (half_form) {
     constexpr int HALF_LDS = 2 * 10 * I16_RP > 65536 ? 2 * 10 * I16_RP : 65536;
-    static const int hpf_env = gank_tune("GANK_IMG16_HALF_PF", 9);
-#define IMG16_LAUNCH_HALF(PF)                                                                             \
-  do {                                                                                                    \
-    gank_prof_tag(0, "img16_conv3x3_kernel<" #PF ", 4, true, false>");                                         \
-    GANK_MAX_DYNAMIC_LDS((img16_conv3x3_kernel<PF, 4, true>), HALF_LDS, "img16_conv3x3");                 \
-    hipLaunchKernelGGL((img16_conv3x3_kernel<PF, 4, true>), dim3(a.main_blocks + a.lb.blocks), dim3(512), HALF_LDS, s, a); \
-  } while (0)
-    switch (hpf_env) {
-#ifdef GANK_TUNING
-      case 6: IMG16_LAUNCH_HALF(6); break;
-      case 18: IMG16_LAUNCH_HALF(18); break;
-#endif
-      default: IMG16_LAUNCH_HALF(9); break;
-    }
-#undef IMG16_LAUNCH_HALF
+    gank_prof_tag(0, "img16_conv3x3_kernel<9, true, false>");
+    GANK_MAX_DYNAMIC_LDS((img16_conv3x3_kernel<9, true>), HALF_LDS, "img16_conv3x3");
+    hipLaunchKernelGGL((img16_conv3x3_kernel<9, true>), dim3(a.main_blocks + a.lb.blocks), dim3(512), HALF_LDS, s, a);
     GANK_LAUNCH_OK("img16_conv3x3");
     gank_prof_end(0, s);
     return 0;
   }
-#define IMG16_LAUNCH(PF, TW)                                                                              \
-  do {                                                                                                    \
-    gank_prof_tag(0, "img16_conv3x3_kernel<" #PF ", " #TW ", false, false>");                                         \
-    GANK_MAX_DYNAMIC_LDS((img16_conv3x3_kernel<PF, TW>), 2 * I16_IMG, "img16_conv3x3");                   \
-    hipLaunchKernelGGL((img16_conv3x3_kernel<PF, TW>), dim3(a.main_blocks + a.lb.blocks), dim3(2048 / TW), 2 * I16_IMG, s, a); \
-  } while (0)
-  switch (cfg_env) {
-#ifdef GANK_TUNING
-    case 406: IMG16_LAUNCH(6, 4); break;
-    case 418: IMG16_LAUNCH(18, 4); break;
-    case 806: IMG16_LAUNCH(6, 8); break;
-    case 812: IMG16_LAUNCH(12, 8); break;
-    case 818: IMG16_LAUNCH(18, 8); break;
-#endif
-    default: IMG16_LAUNCH(12, 4); break;
-  }
-#undef IMG16_LAUNCH
+  // 4 pixel tiles per wave, 12 weight fragments in flight
+  gank_prof_tag(0, "img16_conv3x3_kernel<12, false, false>");
+  GANK_MAX_DYNAMIC_LDS(img16_conv3x3_kernel<12>, 2 * I16_IMG, "img16_conv3x3");
+  hipLaunchKernelGGL(img16_conv3x3_kernel<12>, dim3(a.main_blocks + a.lb.blocks), dim3(512), 2 * I16_IMG, s, a);
   gank_prof_end(0, s);
   GANK_LAUNCH_OK("img16_conv3x3");
   return 0;
@@ -2129,8 +1877,9 @@ struct G8Args {
   int xcd;
 };
 
-template <int C, int PF>
+template <int C>
 __global__ __launch_bounds__(256) void res8_conv3x3_kernel(G8Args a) {
+  constexpr int PF = 12;                             // weight fragments in flight per wave
   using G = G8Geom<C>;
   static_assert(G::STEPS % PF == 0, "ring position");
   constexpr int NT = 256, U = C / 8;                 // U = 16-byte units per pixel
@@ -2293,9 +2042,6 @@ __global__ __launch_bounds__(256) void res8_conv3x3_kernel(G8Args a) {
       tsum += (t4[0] + t4[1]) + (t4[2] + t4[3]);
     }
     float* dst = a.stat_sums + ((long)(n / a.stat_n_per_group) * GANK_STAT_SLOTS + (blockIdx.x % GANK_STAT_SLOTS)) * 2 * a.Cout;
-#ifdef GANK_TUNING
-    if (gank_stats_dbg) return;
-#endif
     atomicAdd(dst + st * a.Cout + co0 + cw, tsum);
   }
 }
@@ -2322,13 +2068,12 @@ extern "C" int gank_res8_conv3x3(const void* x, const void* w_rfrag, const float
   a.stat_sums = stat_sums; a.N = N; a.Cout = Cout;
   a.up_in = (flags & GANK_IN_UPSAMPLE2X) ? 1 : 0; a.res_up = (flags & GANK_RES_UPSAMPLE2X) ? 1 : 0; a.pool_out = pool_out ? 1 : 0;
   a.stat_n_per_group = stat_sums ? N / stat_groups : 1;
-  a.xcd = resident_xcd_env();
+  a.xcd = 1;
   hipStream_t s = (hipStream_t)stream;
   const double px_in = a.up_in ? 16.0 : 64.0, px_out = pool_out ? 16.0 : 64.0;
   gank_prof_begin(0, 2.0 * N * 64.0 * 9.0 * Cin * Cout, s,
                   2.0 * (N * px_in * Cin + 9.0 * Cin * Cout + N * px_out * Cout + (residual ? N * (a.res_up ? 16.0 : 64.0) * Cout : 0.0)));
-  gank_prof_tag(0, Cin == 256 ? "res8_conv3x3_kernel<256, 12>" : "res8_conv3x3_kernel<128, 12>");
-  if (stat_sums) gank_stats_dbg_init();
+  gank_prof_tag(0, Cin == 256 ? "res8_conv3x3_kernel<256>" : "res8_conv3x3_kernel<128>");
   if (stat_sums && !(flags & GANK_STATS_PREZEROED)) {
     const int nz = stat_groups * GANK_STAT_SLOTS * 2 * Cout;
     hipLaunchKernelGGL(g8_zero_kernel, dim3((nz + 255) / 256), dim3(256), 0, s, stat_sums, nz);
@@ -2336,14 +2081,18 @@ extern "C" int gank_res8_conv3x3(const void* x, const void* w_rfrag, const float
   const int grid = N * (Cout / 128);
   if (Cin == 256) {
     constexpr int LDS = G8Geom<256>::IMG > G8_RED_BYTES ? G8Geom<256>::IMG : G8_RED_BYTES;
-    GANK_MAX_DYNAMIC_LDS((res8_conv3x3_kernel<256, 12>), LDS, "res8_conv3x3");
-    hipLaunchKernelGGL((res8_conv3x3_kernel<256, 12>), dim3(grid), dim3(256), LDS, s, a);
+    GANK_MAX_DYNAMIC_LDS((res8_conv3x3_kernel<256>), LDS, "res8_conv3x3");
+    hipLaunchKernelGGL((res8_conv3x3_kernel<256>), dim3(grid), dim3(256), LDS, s, a);
   } else {
     constexpr int LDS = G8Geom<128>::IMG > G8_RED_BYTES ? G8Geom<128>::IMG : G8_RED_BYTES;
-    GANK_MAX_DYNAMIC_LDS((res8_conv3x3_kernel<128, 12>), LDS, "res8_conv3x3");
-    hipLaunchKernelGGL((res8_conv3x3_kernel<128, 12>), dim3(grid), dim3(256), LDS, s, a);
+    GANK_MAX_DYNAMIC_LDS((res8_conv3x3_kernel<128>), LDS, "res8_conv3x3");
+    hipLaunchKernelGGL((res8_conv3x3_kernel<128>), dim3(grid), dim3(256), LDS, s, a);
   }
   gank_prof_end(0, s);
   GANK_LAUNCH_OK("res8_conv3x3");
   return 0;
 }
+
+// Instantiations no launch reaches (see cpool_res_dgrad_ks_kernel): kept in the code object until their removal comes with its own measurement.
+template __global__ void cpool_res_dgrad_ks_kernel<16, 16>(CpBwdArgs);
+template __global__ void cpool_res_dgrad_ks_kernel<8, 16>(CpBwdArgs);

@@ -40,7 +40,8 @@ struct WgradArgs {
   // consecutive logical ids = share an XCD's L2; 0 = the split index fastest (tiles of a split land on all eight XCDs unless
   // the split count happens to be a multiple of 8, and every XCD then pulls the whole operand through the fabric)
   int xcd;
-  int dbg;            // TUNING builds only (GANK_WGRAD_DBG): 1 = no output (timing of everything but the partial-tile stores / atomics), 2 = one step per block; rows kernel: 4 = no MFMA section, 8 = no global loads in the loop, 16 = no LDS stores, 32 = no barrier
+  int dbg;            // unused (always 0), NOT dead: without it the four filter-row kernels compile to a different instruction schedule
+                      // (33 diff hunks each against the measured one, profiles/knob_retirement.txt) -- removing it is a performance change
   // batched launch of up to 4 same-shape layers (gank_conv2d_wgrad_batched): blockIdx.y (xcd: the logical id) picks the operand set
   int nbatch;
   const bf16* xs[4];
@@ -310,9 +311,6 @@ __global__ __launch_bounds__(WA* WB * 64) void conv_wgrad_kernel(WgradArgs a) {
 
   // D[i][j]: row i = ci (reg&3)+8*(reg>>2)+4*(lane>>5), col j = co = lane&31
   const int r = lane & 31, h = lane >> 5;
-#ifdef GANK_TUNING
-  if (a.dbg & 16) { if (acc[0][0][0] == 123.456f) a.dw[0] = 1.f; return; }
-#endif
 #pragma unroll
   for (int i = 0; i < TA; i++) {
 #pragma unroll
@@ -375,18 +373,13 @@ static void wgrad_slab_setup(WgradArgs& a) {
   a.slab_job->slabs = a.slab_ws;
   a.slab_job->nslabs = a.splits;
 }
-static int wgrad_xcd_env() {
-  static const int v = gank_tune("GANK_WGRAD_XCD", 1);   // experiment knob: 0 = split-fastest block order without the XCD remap (WgradArgs.xcd)
-  return v;
-}
-static int wgrad_round_down_env() {
-  static const int v = gank_tune("GANK_WGRAD_ROUND_DOWN", 1);   // experiment knob: GANK_WGRAD_ROUND_DOWN=0 restores ceil(target / tiles) pixel splits
-  return v;
-}
+constexpr int WGRAD_BLOCKS = 256;     // workgroups a split launch aims at: one per CU
+constexpr int WGRAD_MIN_STEPS = 8;    // 64-pixel steps per block, at least
 constexpr int SUBS = 2048 + 32;   // sub-tile stride in bf16 elements
 
-template <int WA, int WB, int TA, int TB, int PF, int MODE>
+template <int WA, int WB, int TA, int TB, int MODE>
 __global__ __launch_bounds__(WA* WB * 64) void conv_wgrad_lean_kernel(WgradArgs a) {
+  constexpr int PF = 2;                              // slots of the register ring
   constexpr int NT = WA * WB * 64;
   constexpr int CiT = WA * TA * 32, CoT = WB * TB * 32;
   constexpr int SUBA = CiT / 32, SUBB = CoT / 32;
@@ -545,7 +538,7 @@ __global__ __launch_bounds__(WA* WB * 64) void conv_wgrad_lean_kernel(WgradArgs 
   auto step = [&](int s, auto slot) {
     constexpr int D = decltype(slot)::value;
     const int buf = s & 1;
-    if constexpr (PF > 1) load_next(rA[D], rB[D]);
+    load_next(rA[D], rB[D]);
     const bf16* pA = sA + (buf * SUBA + wave_a * TA) * SUBS + tr_off;
     const bf16* pB = sB + (buf * SUBB + wave_b * TB) * SUBS + tr_off;
 #pragma unroll
@@ -572,7 +565,6 @@ __global__ __launch_bounds__(WA* WB * 64) void conv_wgrad_lean_kernel(WgradArgs 
           acc[i][j] = GANK_MFMA32(fa[i], fb[j], acc[i][j]);
     }
     if (s + 1 < nsteps) {
-      if constexpr (PF == 1) load_next(rA[0], rB[0]);
       store_step(buf ^ 1, rA[(D + 1) % PF], rB[(D + 1) % PF]);
     }
     __syncthreads();
@@ -580,19 +572,12 @@ __global__ __launch_bounds__(WA* WB * 64) void conv_wgrad_lean_kernel(WgradArgs 
 
   int s0 = 0;
   for (; s0 + PF <= nsteps; s0 += PF) {
-    if constexpr (PF >= 1) step(s0 + 0, std::integral_constant<int, 0>{});
-    if constexpr (PF >= 2) step(s0 + 1, std::integral_constant<int, 1 % PF>{});
-    if constexpr (PF >= 3) step(s0 + 2, std::integral_constant<int, 2 % PF>{});
-    if constexpr (PF >= 4) step(s0 + 3, std::integral_constant<int, 3 % PF>{});
+    step(s0 + 0, std::integral_constant<int, 0>{});
+    step(s0 + 1, std::integral_constant<int, 1>{});
   }
-  if constexpr (PF >= 2) { if (s0 + 0 < nsteps) step(s0 + 0, std::integral_constant<int, 0>{}); }
-  if constexpr (PF >= 3) { if (s0 + 1 < nsteps) step(s0 + 1, std::integral_constant<int, 1 % PF>{}); }
-  if constexpr (PF >= 4) { if (s0 + 2 < nsteps) step(s0 + 2, std::integral_constant<int, 2 % PF>{}); }
+  if (s0 < nsteps) step(s0, std::integral_constant<int, 0>{});
 
   const int r = lane & 31, h = lane >> 5;
-#ifdef GANK_TUNING
-  if (a.dbg & 16) { if (acc[0][0][0] == 123.456f) DW[0] = 1.f; return; }
-#endif
 #pragma unroll
   for (int i = 0; i < TA; i++) {
 #pragma unroll
@@ -631,30 +616,28 @@ __global__ __launch_bounds__(WA* WB * 64) void conv_wgrad_lean_kernel(WgradArgs 
   }
 }
 
-template <int WA, int WB, int TA, int TB, int PF, int MODE>
+template <int WA, int WB, int TA, int TB, int MODE>
 static int launch_wgrad_lean_mode(WgradArgs a, hipStream_t s) {
   constexpr int CiT = WA * TA * 32, CoT = WB * TB * 32;
   a.tiles_ci = cdiv(a.Cin, CiT);
   a.tiles_co = cdiv(a.Cout, CoT);
   const int total_steps = a.M / 64;
   const long tiles = (long)a.taps * a.tiles_ci * a.tiles_co * (a.nbatch > 0 ? a.nbatch : 1);   // grid.y layers fill the chip too
-  static const int target_env = gank_tune("GANK_WGRAD_SPLIT_TARGET", 256), minsteps_env = gank_tune("GANK_WGRAD_MIN_STEPS", 8);
-  int splits = (int)((target_env + tiles - 1) / tiles);
-  if (splits > total_steps / minsteps_env) splits = total_steps / minsteps_env;
+  int splits = (int)((WGRAD_BLOCKS + tiles - 1) / tiles);
+  if (splits > total_steps / WGRAD_MIN_STEPS) splits = total_steps / WGRAD_MIN_STEPS;
   if (splits < 1) splits = 1;
   a.steps_per_split = cdiv(total_steps, splits);
   a.splits = cdiv(total_steps, a.steps_per_split);
   size_t lds = (size_t)2 * (CiT / 32 + CoT / 32) * SUBS * sizeof(bf16);
   const size_t red = (size_t)WA * WB * 64 * (64 * CoT / 8 / (WA * WB * 64)) * 8 * sizeof(float);
   if (red > lds) lds = red;
-  auto kern = conv_wgrad_lean_kernel<WA, WB, TA, TB, PF, MODE>;
+  auto kern = conv_wgrad_lean_kernel<WA, WB, TA, TB, MODE>;
   GANK_MAX_DYNAMIC_LDS(kern, (int)lds, "conv_wgrad");
   const long grid = tiles / (a.nbatch > 0 ? a.nbatch : 1) * a.splits;
   GANK_REQUIRE(grid < (1L << 30), "conv_wgrad: grid too large");
-  static const std::string tag = gank_format("conv_wgrad_lean_kernel<%d, %d, %d, %d, %d, %d>", WA, WB, TA, TB, PF, MODE);     // magic static: built once, thread-safe
+  static const std::string tag = gank_format("conv_wgrad_lean_kernel<%d, %d, %d, %d, %d>", WA, WB, TA, TB, MODE);     // magic static: built once, thread-safe
   gank_prof_tag(1, tag.c_str());
   wgrad_slab_setup(a);
-  { static const int dbg_ = gank_tune("GANK_WGRAD_DBG", 0); a.dbg = dbg_; }
   long gx = grid;
   a.d1_blocks = 0;
   if (a.d1_dx && a.nbatch <= 0 && WA * WB * 64 == 256 && TA == 1 && TB == 1 && MODE == 0 && a.ks == 1) {
@@ -668,18 +651,18 @@ static int launch_wgrad_lean_mode(WgradArgs a, hipStream_t s) {
   return 0;
 }
 
-template <int WA, int WB, int TA, int TB, int PF>
+template <int WA, int WB, int TA, int TB>
 static int launch_wgrad_lean(const WgradArgs& a, hipStream_t s) {
   const int mode = ((a.flags & GANK_IN_RELU) ? 1 : 0) | ((a.flags & GANK_IN_UPSAMPLE2X) ? 2 : 0) |
                    ((a.flags & GANK_DY_UPSAMPLE2X) ? 4 : 0) | ((a.flags & WG_X_STRIDE2) ? 8 : 0);
   switch (mode) {
-    case 8: return launch_wgrad_lean_mode<WA, WB, TA, TB, PF, 8>(a, s);
-    case 9: return launch_wgrad_lean_mode<WA, WB, TA, TB, PF, 9>(a, s);
-    case 0: return launch_wgrad_lean_mode<WA, WB, TA, TB, PF, 0>(a, s);
-    case 1: return launch_wgrad_lean_mode<WA, WB, TA, TB, PF, 1>(a, s);
-    case 2: return launch_wgrad_lean_mode<WA, WB, TA, TB, PF, 2>(a, s);
-    case 4: return launch_wgrad_lean_mode<WA, WB, TA, TB, PF, 4>(a, s);
-    case 5: return launch_wgrad_lean_mode<WA, WB, TA, TB, PF, 5>(a, s);
+    case 8: return launch_wgrad_lean_mode<WA, WB, TA, TB, 8>(a, s);
+    case 9: return launch_wgrad_lean_mode<WA, WB, TA, TB, 9>(a, s);
+    case 0: return launch_wgrad_lean_mode<WA, WB, TA, TB, 0>(a, s);
+    case 1: return launch_wgrad_lean_mode<WA, WB, TA, TB, 1>(a, s);
+    case 2: return launch_wgrad_lean_mode<WA, WB, TA, TB, 2>(a, s);
+    case 4: return launch_wgrad_lean_mode<WA, WB, TA, TB, 4>(a, s);
+    case 5: return launch_wgrad_lean_mode<WA, WB, TA, TB, 5>(a, s);
     default: return -1;   // combination not instantiated: caller falls back to the general kernel
   }
 }
@@ -824,9 +807,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_packed_kernel(WgradArgs a) {
   if (s0 + 1 < nsteps) step(s0 + 1, std::integral_constant<int, 1>{});
 
   const int r = lane & 31, h = lane >> 5;
-#ifdef GANK_TUNING
-  if (a.dbg & 16) { if (acc[0] == 123.456f) a.dw[0] = 1.f; return; }
-#endif
 #pragma unroll
   for (int e = 0; e < 16; e++) {
     const int row = (e & 3) + 8 * (e >> 2) + 4 * h;      // MFMA row index 0..31, col = r
@@ -872,10 +852,8 @@ static int launch_wgrad_packed(WgradArgs a, hipStream_t s) {
   const int Cw = PACK_X ? a.Cout : a.Cin;
   const int tiles = cdiv(Cw, 128);
   const int total_steps = cdiv(a.M, 64);
-  static const int target = gank_tune("GANK_WGRAD_PACKED_BLOCKS", 256);   // experiment knob: GANK_WGRAD_PACKED_BLOCKS (blocks per launch; every block ends in 32 x 128 float atomics)
-  int splits = target / tiles;
-  static const int minsteps = gank_tune("GANK_WGRAD_PACKED_MINSTEPS", 8);   // experiment knob: GANK_WGRAD_PACKED_MINSTEPS (64-pixel steps per block, at least)
-  if (splits > total_steps / minsteps) splits = total_steps / minsteps;
+  int splits = WGRAD_BLOCKS / tiles;   // every block ends in 32 x 128 float atomics
+  if (splits > total_steps / WGRAD_MIN_STEPS) splits = total_steps / WGRAD_MIN_STEPS;
   if (splits < 1) splits = 1;
   a.steps_per_split = cdiv(total_steps, splits);
   a.splits = cdiv(total_steps, a.steps_per_split);
@@ -883,7 +861,6 @@ static int launch_wgrad_packed(WgradArgs a, hipStream_t s) {
   auto kern = conv_wgrad_packed_kernel<PACK_X>;
   gank_prof_tag(1, PACK_X ? "conv_wgrad_packed_kernel<true>" : "conv_wgrad_packed_kernel<false>");
   wgrad_slab_setup(a);
-  { static const int dbg_ = gank_tune("GANK_WGRAD_DBG", 0); a.dbg = dbg_; }
   hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * a.splits)), dim3(256), lds, s, a);
   GANK_LAUNCH_OK("conv_wgrad_packed");
   return 0;
@@ -1067,8 +1044,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_narrow_stream_kernel(NarrowWgA
 }
 
 static bool wgrad_narrow_stream_ok(int N, int H, int W, int Cin, int Cout, int ks) {
-  static const int env = gank_tune("GANK_WGRAD_STREAM", 1);   // experiment knob: GANK_WGRAD_STREAM=0 keeps the packed kernel
-  return env && Cin == 3 && (ks == 1 || ks == 3) && Cout % 128 == 0 && (512 + 2 * W + 2) * 6 + 16 <= 4096 && (long)N * H * W * Cout * 2 < (1L << 31) && (long)N * H * W < (1L << 30);
+  return Cin == 3 && (ks == 1 || ks == 3) && Cout % 128 == 0 && (512 + 2 * W + 2) * 6 + 16 <= 4096 && (long)N * H * W * Cout * 2 < (1L << 31) && (long)N * H * W < (1L << 30);
 }
 static NarrowWgArgs narrow_args(const void* x, const void* dy, float* dw, float* dbias, int N, int H, int W, int Cout, float scale) {
   NarrowWgArgs q{};
@@ -1082,12 +1058,11 @@ static int launch_wgrad_narrow_stream(const NarrowWgArgs& a0, int ks0, const Nar
   NarrowWgArgs b1 = a1;
   if (!ks1) b1.blocks = 0;
   // fold the second layer into the first one's blocks when it has exactly a quarter of the pixels (and the same couts)
-  // GANK_NARROW_FOLD=1: every block takes 512 pixels of the first layer and then 128 of the second (one round of blocks instead of
-  // 256 + 64).  Isolated it is faster (scratch/micro/narrow.hip: 16.8 vs 18.6 us warm, 24.2 vs 28.3 us from cold caches); inside the
+  // (every block takes 512 pixels of the first layer and then 128 of the second: one round of blocks instead of 256 + 64).
+  // Isolated the folded form is faster (scratch/micro/narrow.hip: 16.8 vs 18.6 us warm, 24.2 vs 28.3 us from cold caches); inside the
   // critic update it measured 0.5 % SLOWER per iteration (interleaved A/B on one box), so separate block ranges stay the default.
-  static const int fold_env = gank_tune("GANK_NARROW_FOLD", 0);
-  const int folded = fold_env && ks1 && a0.Cout == a1.Cout && a0.M == 4 * a1.M && a0.M % 512 == 0 ? 1 : 0;
-  const int grid = folded ? a0.blocks : a0.blocks + b1.blocks;
+  const int folded = 0;
+  const int grid = a0.blocks + b1.blocks;
 #define NARROW_LAUNCH(K0, K1)                                                                                      \
   do {                                                                                                             \
     auto kern = conv_wgrad_narrow_stream_kernel<K0, K1, 3>;                                                        \
@@ -1115,8 +1090,9 @@ static int launch_wgrad_narrow_stream(const NarrowWgArgs& a0, int ks0, const Nar
 // ------------------------------------------------------------------------------------------------------
 constexpr int XSUB = 100 * 32 + 32;   // halo sub-tile stride (bf16): 64 B off a 256 B multiple
 
-template <int MODE, int PF>
+template <int MODE>
 __global__ __launch_bounds__(256) void conv_wgrad_taps_kernel(WgradArgs a) {
+  constexpr int PF = 2;                              // register prefetch depth (steps)
   constexpr int NT = 256;
   constexpr bool XRELU = (MODE & 1) != 0, XUP = (MODE & 2) != 0, DYUP = (MODE & 4) != 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1246,8 +1222,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_taps_kernel(WgradArgs a) {
   auto step = [&](int s, auto slot) {
     constexpr int D = decltype(slot)::value;
     const int buf = s & 1;
-    if constexpr (PF > 1) load_next(rX[D], rD[D]);
-    else if (s + 1 < nsteps) load_next(rX[0], rD[0]);
+    load_next(rX[D], rD[D]);
     const bf16* pX = sX + (buf * 2 + wave_a) * XSUB + xl;
     const bf16* pD = sD + (buf * 2 + wave_b) * SUBS + dl;
 #pragma unroll
@@ -1270,9 +1245,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_taps_kernel(WgradArgs a) {
   int s0 = 0;
   for (; s0 + PF <= nsteps; s0 += PF) {
     step(s0 + 0, std::integral_constant<int, 0>{});
-    if constexpr (PF >= 2) step(s0 + 1, std::integral_constant<int, 1 % PF>{});
+    step(s0 + 1, std::integral_constant<int, 1>{});
   }
-  if constexpr (PF >= 2) { if (s0 < nsteps) step(s0, std::integral_constant<int, 0>{}); }
+  if (s0 < nsteps) step(s0, std::integral_constant<int, 0>{});
 
   // partial tile -> slab [split][tap][Cin][Cout] (plain stores) or atomics straight into dw
   const int r = lane & 31, h = lane >> 5;
@@ -1323,13 +1298,9 @@ __global__ void wgrad_reduce_slabs_kernel(const float* __restrict__ ws, float* _
   }
 }
 
-static int wgrad_taps_min_m() {
-  static const int v = gank_tune("GANK_WGRAD_TAPS_MINM", 16384);   // experiment knob
-  return v;
-}
 static bool wgrad_taps_ok(const WgradArgs& a) {
   return a.ks == 3 && a.pad == 1 && !(a.flags & WG_X_STRIDE2) && a.sw >= 3 && a.shw >= 6 && a.H >= 8 && a.W >= 8 &&
-         (a.M >= wgrad_taps_min_m() || (a.M >= 8192 && (a.Cin / 64) * (a.Cout / 64) >= 64)) &&   // small reductions go to the filter-row kernel unless the channel tiles alone fill the chip
+         (a.M >= 16384 || (a.M >= 8192 && (a.Cin / 64) * (a.Cout / 64) >= 64)) &&   // small reductions go to the filter-row kernel unless the channel tiles alone fill the chip
          a.Cin % 64 == 0 && a.Cout % 64 == 0 && (a.M % 64 == 0) &&
          (long)a.N * a.Hx * a.Wx * a.Cin < (1L << 30) && (long)a.N * a.Hdy * a.Wdy * a.Cout < (1L << 30);
 }
@@ -1339,8 +1310,7 @@ static void wgrad_taps_geometry(WgradArgs& a) {
   a.tiles_co = a.Cout / 64;
   const int total_steps = a.M / 64;
   const int tiles = a.tiles_ci * a.tiles_co;
-  static const int target = gank_tune("GANK_WGRAD_TAPS_TARGET", 256);   // experiment knob // one workgroup per CU: 384 leaves a half-empty second round, 512 doubles the slab traffic
-  int splits = (target + tiles - 1) / tiles;
+  int splits = (WGRAD_BLOCKS + tiles - 1) / tiles;   // one workgroup per CU: 384 leaves a half-empty second round, 512 doubles the slab traffic
   if (splits > total_steps / 4) splits = total_steps / 4;
   if (splits < 1) splits = 1;
   a.steps_per_split = cdiv(total_steps, splits);
@@ -1357,17 +1327,11 @@ static int launch_wgrad_taps_mode(WgradArgs a, hipStream_t s) {
     a.ws = nullptr;   // atomics
   }
   size_t lds = (size_t)2 * 2 * (XSUB + SUBS) * sizeof(bf16);
-  static const int tpf = gank_tune("GANK_WGRAD_TAPS_PF", 2);
-#ifdef GANK_TUNING
-  auto kern = tpf == 1 ? conv_wgrad_taps_kernel<MODE, 1> : conv_wgrad_taps_kernel<MODE, 2>;
-#else
-  (void)tpf;
-  auto kern = conv_wgrad_taps_kernel<MODE, 2>;
-#endif
-  static const std::string tag = gank_format("conv_wgrad_taps_kernel<%d, 2> + wgrad_reduce_slabs_kernel", MODE);     // magic static: built once, thread-safe
-  static const std::string tag_deferred = gank_format("conv_wgrad_taps_kernel<%d, 2>", MODE);      // (the slab reduction is a job of the caller's summing launch)
+  auto kern = conv_wgrad_taps_kernel<MODE>;
+  static const std::string tag = gank_format("conv_wgrad_taps_kernel<%d> + wgrad_reduce_slabs_kernel", MODE);     // magic static: built once, thread-safe
+  static const std::string tag_deferred = gank_format("conv_wgrad_taps_kernel<%d>", MODE);      // (the slab reduction is a job of the caller's summing launch)
   gank_prof_tag(1, (a.ws && a.slab_job && a.splits <= 32) ? tag_deferred.c_str() : tag.c_str());
-  a.xcd = wgrad_xcd_env();
+  a.xcd = 1;
   a.main_blocks = a.tiles_ci * a.tiles_co * a.splits;
   if (a.rider_blocks > 0) {
     GANK_REQUIRE(a.ws && a.slab_job && a.splits <= 32 && a.Hdy == a.H && a.Wdy == a.W, "conv_wgrad_taps: the tap-sums rider needs the deferred slab form");
@@ -1419,6 +1383,9 @@ constexpr int CPR_XSUB = 8 * 18 * 32 + 32;   // sub-tile stride (bf16) of the wi
 // patch) -- for layers too small for the all-taps kernel (its 9-tap partial tiles, one per pixel split, cost more slab
 // traffic than the layer has FLOPs); partial tiles are added to dw with fp32 atomics (a third of the all-taps volume per
 // block) or written to slabs when a workspace is given.  grid.y = layer of a same-shape batch (nbatch > 0).
+// KG = 3 is the form every launch uses.  KG = 1 (256 threads, every wave feeds and computes) and KG = 2 lost their A/B runs
+// (profiles/r05_rows_kernel_loop.txt) and are reached by no launch; they are still instantiated at the end of this file because the
+// surviving kernels ran 0.1 - 0.2 % of the training step slower without them in the code object (profiles/knob_retirement.txt).
 // KG = 2: 512 threads, the two wave groups take the first / second pixel-row pairs of every patch (two waves per SIMD: one
 // group's transposed reads run under the other's MFMAs; with one wave per SIMD a step took ~1300 cycles against 512 of LDS
 // reads and 384 of MFMA) and the second group's partial tile is added through LDS at the end -- same slab volume.
@@ -1426,8 +1393,9 @@ constexpr int CPR_XSUB = 8 * 18 * 32 + 32;   // sub-tile stride (bf16) of the wi
 // to the other LDS buffer (one barrier per step as before).  In the one-role form a step was the SUM of its MFMA section (0.25 us),
 // its 20 buffer loads (0.2 us, the same with out-of-range addresses: issue through the CU's one address unit, not memory) and
 // its 20 16-byte LDS stores (0.2 us): every wave stalled on the load issue in the middle of its MFMA stream.
-template <int MODE, int PF, bool S2, int KG = 1>
+template <int MODE, bool S2, int KG>
 __global__ __launch_bounds__(KG == 3 ? 512 : 256 * KG) void conv_wgrad_rows_kernel(WgradArgs a) {
+  constexpr int PF = 2;                              // register prefetch depth (patches)
   constexpr bool SPEC = KG == 3;
   constexpr int NT = SPEC ? 256 : 256 * KG, NDC = 512 / NT, KPG = SPEC ? 4 : 4 / KG;      // NT = staging threads
   constexpr bool XRELU = (MODE & 1) != 0;
@@ -1476,9 +1444,6 @@ __global__ __launch_bounds__(KG == 3 ? 512 : 256 * KG) void conv_wgrad_rows_kern
   int nsteps = (a.M >> 6) - step0;
   if (nsteps > a.steps_per_split) nsteps = a.steps_per_split;
   if (nsteps <= 0) return;
-#ifdef GANK_TUNING
-  if (a.dbg & 2) nsteps = 1;
-#endif
 
   constexpr int OOB = 0x7FFFFFF0;
   const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(X), 0, a.N * a.Hx * a.Wx * a.Cin * 2, 0x00020000);
@@ -1526,18 +1491,12 @@ __global__ __launch_bounds__(KG == 3 ? 512 : 256 * KG) void conv_wgrad_rows_kern
     for (int j = 0; j < NXC; j++) {
       const int iy = ST * py0 + x_hy[j], ix = ST * px0 + x_hx[j];
       bool ok = (unsigned)iy < (unsigned)a.Hx && (unsigned)ix < (unsigned)a.Wx;
-#ifdef GANK_TUNING
-      if (a.dbg & 64) ok = false;            // timing only: x reads out of range (zero fill, no memory traffic)
-#endif
       const int off = ((n * a.Hx + iy) * a.Wx + ix) * a.Cin * 2 + x_c[j];
       rX[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, ok ? off : OOB, 0, 0);
     }
 #pragma unroll
     for (int j = 0; j < NDC; j++) {
       int off = ((n * a.H + py0 + d_y[j]) * a.W + px0 + d_x[j]) * a.Cout * 2 + d_c[j];
-#ifdef GANK_TUNING
-      if (a.dbg & 128) off = OOB;            // timing only: dy reads out of range
-#endif
       rD[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_dy, off, 0, 0);
     }
     if (cur < last) cur++;
@@ -1583,18 +1542,11 @@ __global__ __launch_bounds__(KG == 3 ? 512 : 256 * KG) void conv_wgrad_rows_kern
   auto step = [&](int s, auto slot) {
     constexpr int D = decltype(slot)::value;
     const int buf = s & 1;
-#ifdef GANK_TUNING
-    if (!(a.dbg & 8))
-#endif
     if (feeds) {
-      if constexpr (PF > 1) load_next(rX[D], rD[D]);
-      else if (s + 1 < nsteps) load_next(rX[0], rD[0]);
+      load_next(rX[D], rD[D]);
     }
     const bf16* pX = sX + (buf * 2 + wave_a) * CPR_XSUB + xl;
     const bf16* pD = sD + (buf * 2 + wave_b) * SUBS + dl;
-#ifdef GANK_TUNING
-    if (!(a.dbg & 4))
-#endif
     if (computes)
 #pragma unroll
     for (int kk = 0; kk < KPG; kk++) {
@@ -1609,29 +1561,16 @@ __global__ __launch_bounds__(KG == 3 ? 512 : 256 * KG) void conv_wgrad_rows_kern
         acc[t] = GANK_MFMA32(__builtin_bit_cast(bf16x8, ta), fb, acc[t]);
       }
     }
-#ifdef GANK_TUNING
-    if (!(a.dbg & 16))
-#endif
     if (feeds && s + 1 < nsteps) store_step(buf ^ 1, rX[(D + 1) % PF], rD[(D + 1) % PF]);
-#ifdef GANK_TUNING
-    if (!(a.dbg & 32))
-#endif
     __syncthreads();
   };
   int s0 = 0;
   for (; s0 + PF <= nsteps; s0 += PF) {
     step(s0 + 0, std::integral_constant<int, 0>{});
-    if constexpr (PF >= 2) step(s0 + 1, std::integral_constant<int, 1 % PF>{});
-    if constexpr (PF >= 3) step(s0 + 2, std::integral_constant<int, 2 % PF>{});
-    if constexpr (PF >= 4) step(s0 + 3, std::integral_constant<int, 3 % PF>{});
+    step(s0 + 1, std::integral_constant<int, 1>{});
   }
-  if constexpr (PF >= 2) { if (s0 + 0 < nsteps) step(s0 + 0, std::integral_constant<int, 0>{}); }
-  if constexpr (PF >= 3) { if (s0 + 1 < nsteps) step(s0 + 1, std::integral_constant<int, 1 % PF>{}); }
-  if constexpr (PF >= 4) { if (s0 + 2 < nsteps) step(s0 + 2, std::integral_constant<int, 2 % PF>{}); }
+  if (s0 < nsteps) step(s0, std::integral_constant<int, 0>{});
 
-#ifdef GANK_TUNING
-  if (a.dbg & 1) { if (acc[0][0] == 123.456f) DW[0] = 1.f; return; }
-#endif
   if constexpr (KG == 2) {        // second wave group's partial tile -> first group's registers (the loop's last barrier has passed)
     float* xr = reinterpret_cast<float*>(smem);             // [NTAP * 16][256]
     if (kgrp == 1) {
@@ -1686,26 +1625,18 @@ __global__ __launch_bounds__(KG == 3 ? 512 : 256 * KG) void conv_wgrad_rows_kern
   }
 }
 
-static int wgrad_rows_kg() {
-  static const int v = gank_tune("GANK_WGRAD_ROWS_KG", 3);   // experiment knob: 1 = 256 threads, every wave feeds and computes; 2 = two K groups (512 threads); 3 = feeding + computing waves (512 threads)
-  return (v == 2 || v == 3) ? v : 1;
-}
-template <bool S2>
-static size_t wgrad_rows_lds(int kg) {
-  const size_t stage = (size_t)2 * 2 * (CPR_XSUB + SUBS) * sizeof(bf16), xr = kg == 2 ? (size_t)(S2 ? 4 : 3) * 16 * 256 * sizeof(float) : 0;
-  return stage > xr ? stage : xr;
-}
+constexpr size_t WGRAD_ROWS_LDS = (size_t)2 * 2 * (CPR_XSUB + SUBS) * sizeof(bf16);
+static_assert(WGRAD_ROWS_LDS <= 65536, "below the default dynamic-LDS limit: no attribute call");
 // filter-row kernel for plain 3x3 stride-1 layers below the all-taps kernel's size (single layer or a same-shape batch)
 static bool wgrad_rows_ok(const WgradArgs& a) {
-  static const int env = gank_tune("GANK_WGRAD_ROWS", 1);   // experiment knob: GANK_WGRAD_ROWS=0 keeps these layers on the per-tap kernel
-  return env && a.ks == 3 && a.pad == 1 && (a.flags & ~GANK_IN_RELU) == 0 && a.sw >= 3 && a.shw >= 6 && a.H >= 8 && a.W >= 8 &&
+  return a.ks == 3 && a.pad == 1 && (a.flags & ~GANK_IN_RELU) == 0 && a.sw >= 3 && a.shw >= 6 && a.H >= 8 && a.W >= 8 &&
          a.Hx == a.H && a.Wx == a.W && a.Hdy == a.H && a.Wdy == a.W && a.Cin % 64 == 0 && a.Cout % 64 == 0 && a.M % 64 == 0 &&
          (long)a.N * a.H * a.W * a.Cin < (1L << 30) && (long)a.N * a.H * a.W * a.Cout < (1L << 30);
 }
 static int wgrad_rows_splits(const WgradArgs& a, int nb) {     // the pixel splits launch_wgrad_rows will use for a batch of nb layers
   const int total_steps = a.M / 64, tiles = (a.Cin / 64) * (a.Cout / 64) * 3 * nb;
-  static const int target = gank_tune("GANK_WGRAD_ROWS_TARGET", 256);
-  int splits = wgrad_round_down_env() ? target / tiles : (target + tiles - 1) / tiles;
+  // at most one workgroup per CU: 6 splits x 48 tiles = 288 blocks ran as two rounds on 256 CUs (31 us), 5 x 48 = 240 as one
+  int splits = WGRAD_BLOCKS / tiles;
   if (splits > total_steps / 4) splits = total_steps / 4;
   if (splits < 1) splits = 1;
   return cdiv(total_steps, cdiv(total_steps, splits));
@@ -1714,37 +1645,15 @@ static int launch_wgrad_rows(WgradArgs a, hipStream_t s) {
   const int nb = a.nbatch > 0 ? a.nbatch : 1;
   a.tiles_ci = a.Cin / 64;
   a.tiles_co = a.Cout / 64;
-  const int total_steps = a.M / 64;
-  const int tiles = a.tiles_ci * a.tiles_co * 3 * nb;
-  static const int target = gank_tune("GANK_WGRAD_ROWS_TARGET", 256);   // experiment knob
-  // at most `target` workgroups: 6 splits x 48 tiles = 288 blocks ran as two rounds on 256 CUs (31 us), 5 x 48 = 240 as one
-  int splits = wgrad_round_down_env() ? target / tiles : (target + tiles - 1) / tiles;
-  if (splits > total_steps / 4) splits = total_steps / 4;
-  if (splits < 1) splits = 1;
-  a.steps_per_split = cdiv(total_steps, splits);
-  a.splits = cdiv(total_steps, a.steps_per_split);
+  a.splits = wgrad_rows_splits(a, nb);
+  a.steps_per_split = cdiv(a.M / 64, a.splits);
   a.ws = nullptr;          // partial tiles by fp32 atomics, or (a batched launch with wss[] set) to per-layer slabs [split][9][Cin][Cout]
   if (a.nbatch <= 0) for (int j = 0; j < 4; j++) a.wss[j] = nullptr;
-  const int kg = wgrad_rows_kg();
-  const size_t lds = wgrad_rows_lds<false>(kg);
   const bool relu = (a.flags & GANK_IN_RELU) != 0;
-  static const int pf = gank_tune("GANK_WGRAD_ROWS_PF", 2);   // experiment knob: register prefetch depth
-#ifdef GANK_TUNING
-  auto kern = relu ? (pf == 4 ? conv_wgrad_rows_kernel<1, 4, false> : pf == 3 ? conv_wgrad_rows_kernel<1, 3, false> : conv_wgrad_rows_kernel<1, 2, false>)
-                   : (pf == 4 ? conv_wgrad_rows_kernel<0, 4, false> : pf == 3 ? conv_wgrad_rows_kernel<0, 3, false> : conv_wgrad_rows_kernel<0, 2, false>);
-#else
-  (void)pf;
-  auto kern = relu ? conv_wgrad_rows_kernel<1, 2, false> : conv_wgrad_rows_kernel<0, 2, false>;
-#endif
-  if (kg == 2) kern = relu ? conv_wgrad_rows_kernel<1, 2, false, 2> : conv_wgrad_rows_kernel<0, 2, false, 2>;
-  if (kg == 3) kern = relu ? conv_wgrad_rows_kernel<1, 2, false, 3> : conv_wgrad_rows_kernel<0, 2, false, 3>;
-  static_assert((size_t)2 * 2 * (CPR_XSUB + SUBS) * sizeof(bf16) <= 65536, "below the default dynamic-LDS limit: no attribute call");
-  gank_prof_tag(1, relu ? "conv_wgrad_rows_kernel<1, 2, false>" : "conv_wgrad_rows_kernel<0, 2, false>");
-  a.xcd = wgrad_xcd_env();
-  static const int dbg = gank_tune("GANK_WGRAD_DBG", 0);
-  a.dbg = dbg;
-  if (a.xcd) hipLaunchKernelGGL(kern, dim3((unsigned)(3 * a.tiles_ci * a.tiles_co * a.splits * nb)), dim3(kg == 1 ? 256 : 512), lds, s, a);
-  else hipLaunchKernelGGL(kern, dim3((unsigned)(3 * a.tiles_ci * a.tiles_co * a.splits), nb), dim3(kg == 1 ? 256 : 512), lds, s, a);
+  auto kern = relu ? conv_wgrad_rows_kernel<1, false, 3> : conv_wgrad_rows_kernel<0, false, 3>;
+  gank_prof_tag(1, relu ? "conv_wgrad_rows_kernel<1, false, 3>" : "conv_wgrad_rows_kernel<0, false, 3>");
+  a.xcd = 1;   // one-dimensional grid: the layer of a batch is part of the logical block id
+  hipLaunchKernelGGL(kern, dim3((unsigned)(3 * a.tiles_ci * a.tiles_co * a.splits * nb)), dim3(512), WGRAD_ROWS_LDS, s, a);
   GANK_LAUNCH_OK("conv_wgrad_rows");
   return 0;
 }
@@ -1770,7 +1679,6 @@ static int launch_wgrad(WgradArgs a, hipStream_t s) {
   static const std::string tag = gank_format("conv_wgrad_kernel<%d, %d, %d, %d, %s, %d>", WA, WB, TA, TB, FAST ? "true" : "false", PF);     // magic static: built once, thread-safe
   gank_prof_tag(1, tag.c_str());
   wgrad_slab_setup(a);
-  { static const int dbg_ = gank_tune("GANK_WGRAD_DBG", 0); a.dbg = dbg_; }
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WA * WB * 64), lds, s, a);
   GANK_LAUNCH_OK("conv_wgrad");
   return 0;
@@ -1793,24 +1701,15 @@ int gank_wgrad_dispatch(WgradArgs a, hipStream_t s) {
   const bool dy_grid = (a.flags & GANK_DY_UPSAMPLE2X) || (a.Hdy == a.H && a.Wdy == a.W);
   const bool lean = fast && same_grid && dy_grid && a.sw >= 0 && a.shw >= 0 && (a.M % 64 == 0) &&
                     (long)a.N * a.Hx * a.Wx * a.Cin < (1L << 30) && (long)a.N * a.Hdy * a.Wdy * a.Cout < (1L << 30);
-  static const int taps_env = gank_tune("GANK_WGRAD_TAPS", 1);   // experiment knob: GANK_WGRAD_TAPS=0 disables the all-taps kernel
-  if (taps_env && wgrad_taps_ok(a)) rc = launch_wgrad_taps(a, s);
+  if (wgrad_taps_ok(a)) rc = launch_wgrad_taps(a, s);
   if (rc < 0 && wgrad_rows_ok(a)) rc = launch_wgrad_rows(a, s);
-  static const int lpf_env = gank_tune("GANK_WGRAD_LEAN_PF", 2);   // experiment knob: prefetch depth of the lean kernel
-  (void)lpf_env;
   // 1x1 layers on few pixels (the shortcuts: 2 K - 8 K pixels, 0.5 - 1 GFLOP): the partial tile a workgroup adds with fp32
   // atomics is what it costs (a CU retires one 256-byte atomic instruction per ~50 ns: 64 KB of a 128 x 128 tile = 13 us);
   // 64 x 64 tiles are 16 KB per workgroup and fill the chip four times better
-  static const int small1x1_env = gank_tune("GANK_WGRAD_1X1_SMALL_TILE", 1);
   if (rc < 0 && lean) {
-#ifdef GANK_TUNING
-    if (a.Cin >= 128 && a.Cout >= 128 && lpf_env == 4) rc = launch_wgrad_lean<2, 2, 2, 2, 4>(a, s);
-    else if (a.Cin >= 128 && a.Cout >= 128 && lpf_env == 3) rc = launch_wgrad_lean<2, 2, 2, 2, 3>(a, s);
-    else
-#endif
-    if (small1x1_env && a.ks == 1 && a.M <= 16384 && a.Cin >= 64 && a.Cout >= 64) rc = launch_wgrad_lean<2, 2, 1, 1, 2>(a, s);
-    else if (a.Cin >= 128 && a.Cout >= 128) rc = launch_wgrad_lean<2, 2, 2, 2, 2>(a, s);
-    else if (a.Cin >= 64 && a.Cout >= 64) rc = launch_wgrad_lean<2, 2, 1, 1, 2>(a, s);
+    if (a.ks == 1 && a.M <= 16384 && a.Cin >= 64 && a.Cout >= 64) rc = launch_wgrad_lean<2, 2, 1, 1>(a, s);
+    else if (a.Cin >= 128 && a.Cout >= 128) rc = launch_wgrad_lean<2, 2, 2, 2>(a, s);
+    else if (a.Cin >= 64 && a.Cout >= 64) rc = launch_wgrad_lean<2, 2, 1, 1>(a, s);
   }
   // narrow operands: pack (tap, channel) into <= 32 MFMA columns so the wide operand streams once
   const bool plain = (a.flags == 0) && a.Hx == a.H && a.Wx == a.W && a.Hdy == a.H && a.Wdy == a.W &&      // the packed kernels walk x and dy on one grid
@@ -1881,8 +1780,7 @@ extern "C" int gank_conv2d_wgrad_slab_splits(int N, int H, int W, int Cin, int C
   const bool xup = flags & GANK_IN_UPSAMPLE2X, dyup = flags & GANK_DY_UPSAMPLE2X;
   a.Hx = xup ? H / 2 : H; a.Wx = xup ? W / 2 : W; a.Hdy = dyup ? H / 2 : H; a.Wdy = dyup ? W / 2 : W;
   a.M = N * H * W; a.sw = log2_or_neg(W); a.shw = log2_or_neg(H * W);
-  static const int taps_env = gank_tune("GANK_WGRAD_TAPS", 1);
-  if (!taps_env || !wgrad_taps_ok(a)) return 0;
+  if (!wgrad_taps_ok(a)) return 0;
   wgrad_taps_geometry(a);
   return (a.splits > 1 && a.splits <= 32) ? a.splits : 0;
 }
@@ -2028,8 +1926,7 @@ __global__ void wgrad_cpool_fold_slabs_kernel(const float* __restrict__ ws, floa
 }
 
 static bool wgrad_cpool_rows_ok(int N, int Hp, int Wp, int Cin, int Cout) {
-  static const int env = gank_tune("GANK_CPOOL_ROWS", 1);   // experiment knob: GANK_CPOOL_ROWS=0 falls back to the 16-tap per-tap kernel
-  return env && Hp >= 8 && Wp >= 8 && log2_or_neg(Hp) >= 0 && log2_or_neg(Wp) >= 0 && Cin % 64 == 0 && Cout % 64 == 0 &&
+  return Hp >= 8 && Wp >= 8 && log2_or_neg(Hp) >= 0 && log2_or_neg(Wp) >= 0 && Cin % 64 == 0 && Cout % 64 == 0 &&
          (long)N * 4 * Hp * Wp * Cin < (1L << 30) && (long)N * Hp * Wp * Cout < (1L << 30);
 }
 static void wgrad_cpool_rows_geometry(WgradArgs& a) {
@@ -2037,8 +1934,7 @@ static void wgrad_cpool_rows_geometry(WgradArgs& a) {
   a.tiles_co = a.Cout / 64;
   const int total_steps = a.M / 64;
   const int tiles = a.tiles_ci * a.tiles_co * 4;
-  static const int target = gank_tune("GANK_CPOOL_ROWS_TARGET", 256);   // experiment knob
-  int splits = wgrad_round_down_env() ? target / tiles : (target + tiles - 1) / tiles;
+  int splits = WGRAD_BLOCKS / tiles;
   if (splits > total_steps / 4) splits = total_steps / 4;
   if (splits < 1) splits = 1;
   a.steps_per_split = cdiv(total_steps, splits);
@@ -2080,24 +1976,12 @@ static int convpool3x3_wgrad_impl(const void* x, const void* dy, float* dw, floa
     GANK_REQUIRE(ws_elems >= 16L * Cin * Cout * a.splits, "convpool3x3_wgrad: workspace of %ld floats, need %ld (gank_convpool3x3_wgrad_ws_elems)",
                  ws_elems, 16L * Cin * Cout * a.splits);
     gank_prof_begin(1, 2.0 * a.M * 16.0 * Cin * Cout, s, 2.0 * ((double)N * 4 * Hp * Wp * Cin + (double)a.M * Cout) + 36.0 * Cin * Cout);
-    gank_prof_tag(1, (job && a.splits <= 16 && (reinterpret_cast<uintptr_t>(dw) & 15) == 0) ? "conv_wgrad_rows_kernel<1, 2, true>"
-                                                                                           : "conv_wgrad_rows_kernel<1, 2, true> + wgrad_cpool_fold_slabs_kernel");
-    const int kg = wgrad_rows_kg();
-    const size_t lds = wgrad_rows_lds<true>(kg);
+    gank_prof_tag(1, (job && a.splits <= 16 && (reinterpret_cast<uintptr_t>(dw) & 15) == 0) ? "conv_wgrad_rows_kernel<1, true, 3>"
+                                                                                           : "conv_wgrad_rows_kernel<1, true, 3> + wgrad_cpool_fold_slabs_kernel");
     a.scale = 1.f;
-    static const int pf = gank_tune("GANK_CPOOL_ROWS_PF", 2);   // experiment knob: register prefetch depth
-#ifdef GANK_TUNING
-    auto kern = (flags & GANK_IN_RELU) ? (pf == 3 ? conv_wgrad_rows_kernel<1, 3, true> : conv_wgrad_rows_kernel<1, 2, true>)
-                                       : (pf == 3 ? conv_wgrad_rows_kernel<0, 3, true> : conv_wgrad_rows_kernel<0, 2, true>);
-#else
-    (void)pf;
-    auto kern = (flags & GANK_IN_RELU) ? conv_wgrad_rows_kernel<1, 2, true> : conv_wgrad_rows_kernel<0, 2, true>;
-#endif
-    static_assert((size_t)2 * 2 * (CPR_XSUB + SUBS) * sizeof(bf16) <= 65536, "below the default dynamic-LDS limit: no attribute call");
-    if (kg == 2) kern = (flags & GANK_IN_RELU) ? conv_wgrad_rows_kernel<1, 2, true, 2> : conv_wgrad_rows_kernel<0, 2, true, 2>;
-    if (kg == 3) kern = (flags & GANK_IN_RELU) ? conv_wgrad_rows_kernel<1, 2, true, 3> : conv_wgrad_rows_kernel<0, 2, true, 3>;
-    a.xcd = wgrad_xcd_env();
-    hipLaunchKernelGGL(kern, dim3((unsigned)(4 * a.tiles_ci * a.tiles_co * a.splits)), dim3(kg == 1 ? 256 : 512), lds, s, a);
+    auto kern = (flags & GANK_IN_RELU) ? conv_wgrad_rows_kernel<1, true, 3> : conv_wgrad_rows_kernel<0, true, 3>;
+    a.xcd = 1;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(4 * a.tiles_ci * a.tiles_co * a.splits)), dim3(512), WGRAD_ROWS_LDS, s, a);
     const long plane4 = (long)Cin * Cout / 4;
     if (job && a.splits <= 16 && (reinterpret_cast<uintptr_t>(dw) & 15) == 0) {        // the fold is left to the caller's summing launch
       job->slabs = ws16;
@@ -2168,8 +2052,7 @@ __global__ __launch_bounds__(256) void wgrad_upconv_fold_slabs_kernel(const floa
 }
 
 static bool wgrad_upconv_ok(int N, int H, int W, int Cin, int Cout) {
-  static const int env = gank_tune("GANK_UPCONV_WGRAD_PHASE", 1);   // experiment knob: 0 keeps the all-taps kernel on the upsampled input
-  return env && Cin % 64 == 0 && Cout % 64 == 0 && wgrad_cpool_rows_ok(N, H, W, Cout, Cin);
+  return Cin % 64 == 0 && Cout % 64 == 0 && wgrad_cpool_rows_ok(N, H, W, Cout, Cin);
 }
 
 extern "C" long gank_upconv3x3_wgrad_ws_elems(int N, int H, int W, int Cin, int Cout) {
@@ -2195,15 +2078,10 @@ extern "C" int gank_upconv3x3_wgrad(const void* x_low, const void* dy, float* dw
   GANK_REQUIRE(ws_elems >= 16L * Cin * Cout * a.splits, "upconv3x3_wgrad: workspace of %ld floats, need %ld (gank_upconv3x3_wgrad_ws_elems)", ws_elems,
                16L * Cin * Cout * a.splits);
   gank_prof_begin(1, 2.0 * a.M * 16.0 * Cin * Cout, s, 2.0 * ((double)a.M * Cin + 4.0 * a.M * Cout) + 36.0 * Cin * Cout);
-  gank_prof_tag(1, "conv_wgrad_rows_kernel<0, 2, true> + wgrad_upconv_fold_slabs_kernel");
-  const int kg = wgrad_rows_kg();
-  const size_t lds = wgrad_rows_lds<true>(kg);
+  gank_prof_tag(1, "conv_wgrad_rows_kernel<0, true, 3> + wgrad_upconv_fold_slabs_kernel");
   a.scale = 1.f;
-  a.xcd = wgrad_xcd_env();
-  auto kern = conv_wgrad_rows_kernel<0, 2, true>;
-  if (kg == 2) kern = conv_wgrad_rows_kernel<0, 2, true, 2>;
-  if (kg == 3) kern = conv_wgrad_rows_kernel<0, 2, true, 3>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(4 * a.tiles_ci * a.tiles_co * a.splits)), dim3(kg == 1 ? 256 : 512), lds, s, a);
+  a.xcd = 1;
+  hipLaunchKernelGGL((conv_wgrad_rows_kernel<0, true, 3>), dim3((unsigned)(4 * a.tiles_ci * a.tiles_co * a.splits)), dim3(512), WGRAD_ROWS_LDS, s, a);
   hipLaunchKernelGGL(wgrad_upconv_fold_slabs_kernel, dim3(Cin / 32, Cout / 32, 9), dim3(256), 0, s, ws16, dw, Cin, Cout, a.splits);
   gank_prof_end(1, s);
   GANK_LAUNCH_OK("upconv3x3_wgrad");
@@ -2302,7 +2180,7 @@ static int wgrad_batched_impl(const gank_wgrad_item* items, int count, int N, in
     a.nbatch = nb;
     a.x = a.xs[0]; a.dy = a.dys[0]; a.dw = a.dws[0]; a.dbias = a.dbs[0];
     gank_prof_begin(1, 2.0 * nb * a.M * (double)Cout * a.taps * Cin, s, nb * (2.0 * a.M * ((double)Cin + Cout) + 4.0 * a.taps * Cin * Cout));
-    const int rc = rows ? launch_wgrad_rows(a, s) : launch_wgrad_lean<2, 2, 2, 2, 2>(a, s);
+    const int rc = rows ? launch_wgrad_rows(a, s) : launch_wgrad_lean<2, 2, 2, 2>(a, s);
     gank_prof_end(1, s);
     if (rc) return rc > 0 ? rc : gank_set_error("conv2d_wgrad_batched: mode not instantiated");
     i += nb;
@@ -2327,3 +2205,13 @@ extern "C" int gank_deconv2d_wgrad(const void* x, const void* dy, float* df, int
   a.scale = 1.f;
   return gank_wgrad_dispatch(a, (hipStream_t)stream);
 }
+
+// Instantiations no launch reaches (see conv_wgrad_rows_kernel): kept in the code object until their removal comes with its own measurement.
+template __global__ void conv_wgrad_rows_kernel<0, false, 1>(WgradArgs);
+template __global__ void conv_wgrad_rows_kernel<1, false, 1>(WgradArgs);
+template __global__ void conv_wgrad_rows_kernel<0, true, 1>(WgradArgs);
+template __global__ void conv_wgrad_rows_kernel<1, true, 1>(WgradArgs);
+template __global__ void conv_wgrad_rows_kernel<0, false, 2>(WgradArgs);
+template __global__ void conv_wgrad_rows_kernel<1, false, 2>(WgradArgs);
+template __global__ void conv_wgrad_rows_kernel<0, true, 2>(WgradArgs);
+template __global__ void conv_wgrad_rows_kernel<1, true, 2>(WgradArgs);

@@ -77,19 +77,6 @@ static inline std::string gank_format(const char* fmt, ...) {
   return std::string(buf);
 }
 
-// Tuning constants of the launch dispatchers (split targets, prefetch depths, kernel on/off switches).  A production build
-// bakes the defaults in: no environment lookups on the product path.  An experiment build (GANK_EXTRA_FLAGS=-DGANK_TUNING
-// GANK_LIB_NAME=libgank_tune.so python -m gan_lib_tensorflow_amd.build) reads each one from the environment once, for the A/B
-// sweeps under scratch/.
-static inline int gank_tune(const char* name, int dflt) {
-#ifdef GANK_TUNING
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-#else
-  (void)name;
-  return dflt;
-#endif
-}
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline int roundup(int a, int b) { return (a + b - 1) / b * b; }
 static inline int log2_or_neg(int v) { int s = 0; while ((1 << s) < v) s++; return ((1 << s) == v) ? s : -1; }

@@ -275,7 +275,6 @@ struct SnScaleTable {
 struct SnPrepExtra {
   const float* sigma[PREP_MAX];     // divisor of prep entry i (the scal word of its weight)
   int prep_blocks;
-  int dbg;                          // TUNING builds (GANK_SNB_DBG), timing only: 1 = scale blocks return, 2 = operand blocks return, 4 = label rows return
 };
 // the per-label rows of a small dense layer on an embedding table: out[l] = bf16( bf16(table[l]) (W / sigma) + bias )
 // Consumer side of the fused optimiser tail (below): the power iteration of this forward pass was already run when the weights
@@ -359,11 +358,6 @@ __device__ __forceinline__ int ld_blocks(const SnLabelDense& ld) { return ld.tab
 // nothing the other ranges touch, and every consumer of either comes after the launch.
 __global__ __launch_bounds__(256) void sn_fwd_b_kernel(SnScaleTable st, PrepTable pt, SnPrepExtra px, SnLabelDense ld, SnAdopt ad, CriticFeedArgs fd) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef GANK_TUNING
-  if ((px.dbg & 1) && (int)blockIdx.x < st.nchunks) return;
-  if ((px.dbg & 2) && (int)blockIdx.x >= st.nchunks && (int)blockIdx.x - st.nchunks < px.prep_blocks) return;
-  if ((px.dbg & 4) && (int)blockIdx.x - st.nchunks >= px.prep_blocks && (int)blockIdx.x - st.nchunks < px.prep_blocks + ld_blocks(ld)) return;
-#endif
   if ((int)blockIdx.x >= st.nchunks) {
     const int pb = blockIdx.x - st.nchunks;
     if (pb >= px.prep_blocks + ld_blocks(ld) + ad.blocks) {
@@ -646,7 +640,6 @@ static int sn_forward(const gank_sn_desc* table, int count, const gank_prep_desc
       ad = *adopt;
       ad.blocks = (ad.total + 255) / 256;
     }
-    { static const int dbg_ = gank_tune("GANK_SNB_DBG", 0); px.dbg = dbg_; }
     CriticFeedArgs fd{};
     if (base == 0 && feed) fd = *feed;
     hipLaunchKernelGGL(sn_fwd_b_kernel, dim3(fine + px.prep_blocks + label_blocks + ad.blocks + fd.blocks), dim3(256), 0, s, st, pt, px, ld, ad, fd);
@@ -704,7 +697,6 @@ struct SnAdamArgs {
   int ngaps, sn_blocks;
   long long* bump;        // optional: a step counter that advances by one when bump_when[0] == 0 (below)
   const int* bump_when;
-  int dbg;                // TUNING builds (GANK_SNTAIL_DBG): 1 = no finalize, 2 = return before the publication, 4 = no parameter / slot stores
   int dw_zero;            // every table entry's dW is known to be zero (nothing but this backward pass contributes): neither read nor cleared
 };
 
@@ -833,9 +825,6 @@ __global__ __launch_bounds__(256) void sn_adam_fwd_a_kernel(SnTable t, SnAdamArg
           }
         }
       }
-#ifdef GANK_TUNING
-      if (ad.dbg & 2) { if (w[0][0] == 123.456f) W[0] = 1.f; return; }
-#endif
       // (the updated chunk stays in registers: its stores are issued BEHIND the ticket below, so that the publication of the
       //  partial sums does not wait for 80 KB of parameter / slot / cleared-gradient stores to drain)
       // ---- forward A of the next pass on the updated rows (sn_fwd_a_kernel's register-tile body)
@@ -918,9 +907,6 @@ __global__ __launch_bounds__(256) void sn_adam_fwd_a_kernel(SnTable t, SnAdamArg
       }
       *flag = last;
     }
-#ifdef GANK_TUNING
-    if (!(ad.dbg & 4))
-#endif
     if (fast) {          // the updated chunk, its slots, the cleared gradient slices: beside the ticket's round trip
       const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -938,9 +924,6 @@ __global__ __launch_bounds__(256) void sn_adam_fwd_a_kernel(SnTable t, SnAdamArg
       }
     }
     __syncthreads();
-#ifdef GANK_TUNING
-    if (!(ad.dbg & 1))
-#endif
     if (*flag) sn_fwd_a_finish(d, u_next, nch, part, red, tid);
   }
   if (health) {           // one pair of atomics per wave that saw anything (adam_tf_kernel)
@@ -1029,7 +1012,6 @@ extern "C" int gank_sn_adam_fwd_a(const gank_sn_desc* table, int count, float* c
   ad.dw_zero = (flags & 1) ? 1 : 0;
   GANK_REQUIRE(!bump || bump_when_zero, "sn_adam_fwd_a: a counter to advance needs its condition word");
   ad.bump = (long long*)bump; ad.bump_when = bump_when_zero;
-  { static const int dbg_ = gank_tune("GANK_SNTAIL_DBG", 0); ad.dbg = dbg_; }
   // the table's weights, in buffer order, must be disjoint views of [p, p + n) whose gradient views sit at the same offsets of g
   int order[SN_MAX];
   for (int i = 0; i < count; i++) order[i] = i;

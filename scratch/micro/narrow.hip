@@ -17,12 +17,8 @@ int main() {
   auto conv1 = [&] { gank_conv2d_wgrad(x0, dy0, dw0, db0, nullptr, 0, N, 32, 32, 3, C, 3, 0, 1.f, 0); };
   auto shortc = [&] { gank_conv2d_wgrad(x1, dy1, dw1, db1, nullptr, 0, N, 16, 16, 3, C, 1, 0, 1.f, 0); };
   auto pair = [&] { gank_conv2d_wgrad_narrow_pair(x0, dy0, dw0, db0, N, 32, 32, C, 3, x1, dy1, dw1, db1, N, 16, 16, C, 1, 1.f, 0); };
-  for (const char* mode : {"stream", "packed"}) {
-    setenv("GANK_WGRAD_STREAM", mode[0] == 's' ? "1" : "0", 1);
-    printf("[%s] conv1 3x3 32x32      %.1f us\n", mode, time_us(conv1));
-    printf("[%s] shortcut 1x1 16x16   %.1f us\n", mode, time_us(shortc));
-    break;     // the knob is read once per process: run the binary twice (GANK_WGRAD_STREAM=0) for the packed kernel
-  }
+  printf("conv1 3x3 32x32      %.1f us\n", time_us(conv1));
+  printf("shortcut 1x1 16x16   %.1f us\n", time_us(shortc));
   printf("pair                      %.1f us\n", time_us(pair));
   // cold: caches flushed before every launch (one launch per timing, median of 9)
   std::vector<float> t;

@@ -1,4 +1,4 @@
-"""Check the two-group LDS-DMA conv kernel (GANK_IGEMM_PP=2: all forms) against torch fp32 convolutions."""
+"""Check the two-group LDS-DMA conv kernel against torch fp32 convolutions."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,5 +1,4 @@
-"""in-graph timing of gank_cpool_res_dgrad_image_wgrad (D.Block.1: 128 x 16x16 pooled, 128 channels) against the two launches it replaces.
-TUNING library knob: GANK_IMGWG_DBG (1 = no final atomics, 2 = no filter-gradient section, 4 = no Xcol build)."""
+"""in-graph timing of gank_cpool_res_dgrad_image_wgrad (D.Block.1: 128 x 16x16 pooled, 128 channels) against the two launches it replaces."""
 import sys, os, torch
 sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '.'))
 from gan_lib_tensorflow_amd import kernels as K

@@ -1,5 +1,5 @@
 """in-graph timing (one hipGraph of `reps` launches, HIP events around the replay) of the critic's batched 8x8 filter gradient -- the
-eager loop of bench_critic_wgrad.py is bound by the host's launch rate for kernels this small.  TUNING library knobs: GANK_WGRAD_DBG."""
+eager loop is bound by the host's launch rate for kernels this small."""
 import sys, os, torch
 sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '.'))
 from gan_lib_tensorflow_amd import kernels as K

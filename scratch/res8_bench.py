@@ -1,4 +1,4 @@
-"""time the fused 8x8 residual chain (fwd, bwd) at the critic's shape; GANK_RES8_CFG picks the kernel variant"""
+"""time the fused 8x8 residual chain (fwd, bwd) at the critic's shape"""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
@@ -19,4 +19,4 @@ def timeit(f, reps=300):
     for _ in range(reps): f()
     e1.record(); torch.cuda.synchronize()
     return 1e3 * e0.elapsed_time(e1) / reps
-print("N", n, "cfg", os.environ.get("GANK_RES8_CFG", "default"), "fwd %.1f us  bwd(train) %.1f us  bwd(dx only) %.1f us" % (timeit(fwd), timeit(lambda: bwd(True)), timeit(lambda: bwd(False))))
+print("N", n, "fwd %.1f us  bwd(train) %.1f us  bwd(dx only) %.1f us" % (timeit(fwd), timeit(lambda: bwd(True)), timeit(lambda: bwd(False))))
