@@ -392,3 +392,16 @@ def swd_score(outputs, targets, **kw):
     (float64 [levels], their mean), x 1000.  **kw: nhood_size, nhoods_per_image, dir_repeats, dirs_per_repeat, seed."""
     from ..common.swd import calculate_swd
     return calculate_swd(outputs.float(), targets.float(), **kw)
+
+
+@torch.no_grad()
+def ndb_score(outputs, targets, **kw):
+    """NDB and JSD (common/ndb.py) of generator outputs against their targets, both [N,H,W,C] in [-1, 1] as the model produces /
+    is fed them (any 16-bit or fp32 dtype): both are quantised to uint8 as the sample metrics quantise
+    (msssim.quantize_on_device), the bins are fitted on the targets -> dict(ndb, ndb_over_k, js, bin_proportions_train,
+    bin_proportions_samples, different_bins).  **kw: number_of_bins, significance_level, max_dims, seed, max_iter."""
+    from ..common.msssim import quantize_on_device
+    from ..common.ndb import calculate_ndb
+    if tuple(outputs.shape) != tuple(targets.shape) or outputs.dim() != 4:
+        raise ValueError(f"ndb_score: outputs {tuple(outputs.shape)} and targets {tuple(targets.shape)}, expected two equal [N,H,W,C]")
+    return calculate_ndb(quantize_on_device(targets), quantize_on_device(outputs), **kw)

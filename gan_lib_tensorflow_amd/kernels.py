@@ -2325,6 +2325,110 @@ def swd_sorted_l1(a, b, part=None):
     return part.view(-1)[:dirs * parts].view(dirs, parts)
 
 
+# ------------------------------------------------------------------ NDB / JSD: k-means bins in pixel space (common/ndb.py)
+def ndb_strips(n):
+    """the 64-row strips of `ndb_assign`: the length of its two partial arrays"""
+    return (int(n) + 63) // 64
+
+
+def ndb_group_ws_elems(n, k):
+    """int32 elements of the work space of `ndb_group_rows` for n rows and k labels"""
+    return int(lib().gank_ndb_group_ws_elems(int(n), int(k)))
+
+
+def _ndb_table(what, name, t, n, device):
+    """an int32 [n] device table of the caller's"""
+    if not t.is_cuda:
+        raise RuntimeError(f"gank: {name} must live on the GPU (no CPU path exists)")
+    if t.dtype != I32 or tuple(t.shape) != (n,):
+        raise RuntimeError(f"gank: {what} takes {name} int32 [{n}], got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def ndb_pixel_features(images, dims=None, out=None):
+    """images uint8 [n, ...] on the device (a row is the flat image, P values) and dims int32 [Dsel] (NumPy or tensor; None: all
+    P pixels in order) -> float32 [n, Dp] on the device, Dp = Dsel rounded up to a multiple of 16: the chosen pixels as floats,
+    the padding columns 0 (gank_ndb_pixel_features).  dims outside [0, P) are refused here, because the kernel cannot refuse
+    them.  out float32 [>= n * Dp]: the result buffer, allocated when None."""
+    if not images.is_cuda:
+        raise RuntimeError("gank: images must live on the GPU (no CPU path exists)")
+    if images.dim() < 2 or images.dtype != torch.uint8 or images.numel() == 0:
+        raise RuntimeError(f"gank: ndb_pixel_features takes uint8 images [n, ...], got {tuple(images.shape)} {images.dtype}")
+    n = images.shape[0]
+    p = images.numel() // n
+    if dims is None:
+        dsel = p
+    else:
+        dims = torch.as_tensor(dims if getattr(dims, "flags", None) is None or dims.flags.writeable else dims.copy())
+        if dims.dim() != 1 or dims.dtype != I32 or dims.numel() == 0:
+            raise RuntimeError(f"gank: ndb_pixel_features takes dims int32 [Dsel], got {tuple(dims.shape)} {dims.dtype}")
+        if int(dims.min()) < 0 or int(dims.max()) >= p:
+            raise RuntimeError(f"gank: ndb_pixel_features: dims in [{int(dims.min())}, {int(dims.max())}] are outside [0, {p})")
+        dsel = dims.numel()
+        dims = dims.to(images.device).contiguous()
+    dp = _roundup(dsel, 16)
+    out = _swd_out("ndb_pixel_features", "out", out, n * dp, F32, images.device)
+    _lib.check(lib().gank_ndb_pixel_features(_p(images, torch.uint8, "images"), n, p, _p(dims, I32, "dims"), dsel, _p(out, F32, "out"),
+                                             _stream()), "ndb_pixel_features")
+    return out.view(-1)[:n * dp].view(n, dp)
+
+
+def ndb_assign(x, c, prev=None, label=None, d2=None, part_inertia=None, part_changed=None):
+    """Rows x float32 [n, D] and centroids c float32 [K, D] -> (label int32 [n], d2 float64 [n], part_inertia float64
+    [ndb_strips(n)], part_changed int32 [ndb_strips(n)]) on the device: per row the nearest centroid (a tie to the lowest index)
+    and its squared distance in float64, per strip of 64 rows the sum of those distances and the number of rows whose label
+    differs from prev int32 [n] (0 when prev is None) (gank_ndb_assign).  The four outputs are allocated when None."""
+    _prd_features("ndb_assign", x=x, c=c)
+    if x.shape[1] != c.shape[1]:
+        raise RuntimeError(f"gank: ndb_assign: x {tuple(x.shape)} and c {tuple(c.shape)} differ in the feature width")
+    n, k, strips = x.shape[0], c.shape[0], ndb_strips(x.shape[0])
+    if prev is not None:
+        _ndb_table("ndb_assign", "prev", prev, n, x.device)
+    label = _swd_out("ndb_assign", "label", label, n, I32, x.device)
+    d2 = _swd_out("ndb_assign", "d2", d2, n, F64, x.device)
+    part_inertia = _swd_out("ndb_assign", "part_inertia", part_inertia, strips, F64, x.device)
+    part_changed = _swd_out("ndb_assign", "part_changed", part_changed, strips, I32, x.device)
+    _lib.check(lib().gank_ndb_assign(_p(x, F32, "x"), n, _p(c, F32, "c"), k, x.shape[1], _p(prev, I32, "prev"), _p(label, I32, "label"),
+                                     _p(d2, F64, "d2"), _p(part_inertia, F64, "part_inertia"), _p(part_changed, I32, "part_changed"),
+                                     _stream()), "ndb_assign")
+    return label.view(-1)[:n], d2.view(-1)[:n], part_inertia.view(-1)[:strips], part_changed.view(-1)[:strips]
+
+
+def ndb_group_rows(label, k, count=None, offset=None, perm=None, ws=None):
+    """label int32 [n] on the device, values in [0, k) -> (count int32 [k], offset int32 [k], perm int32 [n]) on the device: the
+    rows per label, their exclusive prefix sum and the row indices sorted by label, stable (gank_ndb_group_rows).  A label
+    outside [0, k) is the caller's error (the kernel clamps it).  count, offset, perm and ws int32 [>= ndb_group_ws_elems(n, k)]:
+    result buffers and work space, allocated when None."""
+    if not label.is_cuda:
+        raise RuntimeError("gank: label must live on the GPU (no CPU path exists)")
+    if label.dim() != 1 or label.dtype != I32:
+        raise RuntimeError(f"gank: ndb_group_rows takes label int32 [n], got {tuple(label.shape)} {label.dtype}")
+    n, k = label.shape[0], int(k)
+    count = _swd_out("ndb_group_rows", "count", count, k, I32, label.device)
+    offset = _swd_out("ndb_group_rows", "offset", offset, k, I32, label.device)
+    perm = _swd_out("ndb_group_rows", "perm", perm, n, I32, label.device)
+    ws = _swd_out("ndb_group_rows", "ws", ws, ndb_group_ws_elems(n, k), I32, label.device)
+    _lib.check(lib().gank_ndb_group_rows(_p(label, I32, "label"), n, k, _p(count, I32, "count"), _p(offset, I32, "offset"),
+                                         _p(perm, I32, "perm"), _p(ws, I32, "ws"), _stream()), "ndb_group_rows")
+    return count.view(-1)[:max(k, 0)], offset.view(-1)[:max(k, 0)], perm.view(-1)[:n]
+
+
+def ndb_centroids(x, perm, count, offset, c):
+    """Rows x float32 [n, D], the grouping of `ndb_group_rows` (perm int32 [n], count and offset int32 [K]) and centroids c
+    float32 [K, D], updated IN PLACE: every cluster with rows becomes the mean of its rows, added in float64 in perm order and
+    rounded once; a cluster without rows keeps its centroid (gank_ndb_centroids).  Returns c."""
+    _prd_features("ndb_centroids", x=x, c=c)
+    if x.shape[1] != c.shape[1]:
+        raise RuntimeError(f"gank: ndb_centroids: x {tuple(x.shape)} and c {tuple(c.shape)} differ in the feature width")
+    n, k = x.shape[0], c.shape[0]
+    _ndb_table("ndb_centroids", "perm", perm, n, x.device)
+    _ndb_table("ndb_centroids", "count", count, k, x.device)
+    _ndb_table("ndb_centroids", "offset", offset, k, x.device)
+    _lib.check(lib().gank_ndb_centroids(_p(x, F32, "x"), n, x.shape[1], _p(perm, I32, "perm"), _p(count, I32, "count"),
+                                        _p(offset, I32, "offset"), k, _p(c, F32, "c"), _stream()), "ndb_centroids")
+    return c
+
+
 # ------------------------------------------------------------------ profiler
 def prof_enable(on):
     lib().gank_prof_enable(int(on))

@@ -96,6 +96,21 @@ class SampleMetrics:
         return sample_swd(self._metric_draw(), real, n, seed, **kw)
 
     @torch.no_grad()
+    def ndb(self, real, n=10000, **kw):
+        """NDB and JSD (common/ndb.py; Richardson & Weiss 2018, section 2: k-means bins of the training images in pixel space, no
+        network, no downloaded weights) of n samples against `real`: an `NDB` (the bins of a training set, fitted once) or
+        training images uint8 [N,H,W,3] at the samples' size, fitted here -> dict(ndb, ndb_over_k, js, bin_proportions_train,
+        bin_proportions_samples, different_bins).  **kw: number_of_bins, significance_level, max_dims, seed, max_iter of `NDB`
+        when `real` is images."""
+        from .common.ndb import NDB, sample_ndb
+        if isinstance(real, NDB):
+            if kw:
+                raise TypeError(f"{type(self).__name__}.ndb: {sorted(kw)} belong to the fit, and `real` is fitted already")
+        else:
+            real = NDB(real, **kw)
+        return sample_ndb(self._metric_draw(), real, n)
+
+    @torch.no_grad()
     def inception_score(self, n=50000, net=None, splits=10, batch_size=100):
         """get_inception_score(n) of the training scripts, on the device throughout (common/inception/inception_score.py):
         n / 100 passes of 100 samples, mapped back to [-1, 1], `net.logits_device` in batches of `batch_size`, the float64

@@ -1032,6 +1032,41 @@ int gank_swd_sort_rows(double* keys, double* tmp, int dirs, int M, unsigned* his
 int gank_swd_sorted_l1_parts(int M);
 int gank_swd_sorted_l1(const double* a, const double* b, int dirs, int M, double* part, void* stream);
 
+/* ---- NDB / JSD: k-means bins in pixel space (common/ndb.py; Richardson & Weiss, "On GANs and GMMs", section 2) -----------
+ * Lloyd's iteration on FLOAT32 features [n,D]: assign -> group_rows -> centroids.  No atomics, every output element is written
+ * by one plain store of its sole owner: two calls on the same data return the same bits.
+ * gank_ndb_pixel_features: img uint8 [n,P] (a flat image per row), dims int32 [Dsel] on the device or NULL (NULL: the first
+ *   Dsel pixels in order); out float32 [n,Dp], Dp = Dsel rounded up to a multiple of 16: out[i][j] = (float) img[i][dims[j]]
+ *   for j < Dsel (0..255 are exact in float32) and 0 for the padding columns, which change no distance.
+ *   Refused: null img / out; n outside 1..2^24; P outside 1..2^30; Dsel outside 1..4096 or > P; out not 16-byte aligned.  dims is
+ *   device memory the host cannot see: an entry outside [0, P) is the caller's error (kernels.ndb_pixel_features checks
+ *   before upload; the kernel clamps it for memory safety only).
+ * gank_ndb_assign: x [n,D] rows, c [K,D] centroids, prev int32 [n] or NULL.  d2_ik = (|x_i|^2 + |c_k|^2) - 2 <x_i, c_k> in
+ *   float64 (the dot products on v_mfma_f64_16x16x4_f64, contraction over the feature axis in feature order in one accumulator;
+ *   the norms by a fixed-order float64 sum), clamped at 0: the bits of the gank_prd_* distances.  A workgroup owns a strip of 64
+ *   rows and walks all ceil(K / 64) centroid tiles; there are no column segments (at N >= 10 000 rows there are >= 157 strips).
+ *   label int32 [n] = argmin_k d2_ik, a tie to the LOWEST k (every merge is the lexicographic minimum of (d2, k), so its order
+ *   cannot matter); d2 float64 [n] = that minimum; part_inertia float64 [ceil(n/64)] = per strip the sum of its rows' d2: the
+ *   value of row r of the strip in lane 4 r of the workgroup, zeros elsewhere and for rows >= n, added by an xor butterfly
+ *   (32, 16, .. 1) inside each wave and then the four waves in index order; part_changed int32 [ceil(n/64)] = the strip's
+ *   number of rows with label != prev (0 when prev is NULL).
+ * gank_ndb_group_rows: label int32 [n] -> count int32 [K] (= bincount), offset int32 [K] (its exclusive prefix sum) and perm
+ *   int32 [n], the stable counting sort of the row indices by label (= argsort(label, stable)); ws int32
+ *   [gank_ndb_group_ws_elems(n, K)] is work space (K x ceil(n / 2048) counters).  Integer sums only.  A label outside [0, K) is
+ *   the caller's error: it is clamped into the range for memory safety only.
+ * gank_ndb_centroids: for a cluster k with count[k] > 0 and every feature j: s = 0.0; for r in perm[offset[k] : offset[k] +
+ *   count[k]], in that order: s += (double) x[r][j]; c[k][j] = (float)(s / count[k]) -- one float64 accumulator per (k, j), no
+ *   split of a cluster's rows, so the result does not depend on the grid.  A cluster with count[k] == 0 keeps its centroid:
+ *   nothing is written.  perm, count and offset are device memory the host cannot see (clamped for memory safety only).
+ *   Refused by assign, group_rows and centroids: null pointers (prev may be NULL); D % 16 != 0 or D outside 16..4096 (the rule
+ *   of gank_kid_block_sums); K outside 1..1024; n outside 1..2^24; x / c not 16-byte aligned. */
+int gank_ndb_pixel_features(const unsigned char* img, int n, int P, const int* dims, int Dsel, float* out, void* stream);
+int gank_ndb_assign(const float* x, int n, const float* c, int K, int D, const int* prev, int* label, double* d2, double* part_inertia,
+                    int* part_changed, void* stream);
+long gank_ndb_group_ws_elems(int n, int K);
+int gank_ndb_group_rows(const int* label, int n, int K, int* count, int* offset, int* perm, int* ws, void* stream);
+int gank_ndb_centroids(const float* x, int n, int D, const int* perm, const int* count, const int* offset, int K, float* c, void* stream);
+
 /* ---- Pix2Pix input pipeline (Pix2Pix/train.py of the reference) --------------------------------------------------------
  * gank_pix2pix_load_examples: load_examples (train.py:355-431) for a batch, one launch.  raw: uint8 [N,H,Wraw,3] on the
  *   device, 4-byte aligned.  mode 0: pair, A | B of Wraw/2 columns (:395-396); 1: multiple_A, three panels of Wraw/3, A = the
