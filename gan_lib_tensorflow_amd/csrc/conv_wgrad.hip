@@ -1298,8 +1298,15 @@ __global__ void wgrad_reduce_slabs_kernel(const float* __restrict__ ws, float* _
   }
 }
 
+// x (after the fused upsample) covers exactly dy's grid.  The all-taps and lean kernels index x by dy's pitch and bound their taps by
+// dy's size; the general entry (gank_conv2d_general_wgrad) also brings inputs that are larger or smaller than that -- VALID windows,
+// an upsampled input whose output stops short of it -- and those stay on the per-tap kernel, which bounds by x's own size.
+static bool wgrad_x_on_dy_grid(const WgradArgs& a) {
+  return (a.flags & GANK_IN_UPSAMPLE2X) ? (a.H == 2 * a.Hx && a.W == 2 * a.Wx) : (a.Hx == a.H && a.Wx == a.W);
+}
+
 static bool wgrad_taps_ok(const WgradArgs& a) {
-  return a.ks == 3 && a.pad == 1 && !(a.flags & WG_X_STRIDE2) && a.sw >= 3 && a.shw >= 6 && a.H >= 8 && a.W >= 8 &&
+  return a.ks == 3 && a.pad == 1 && !(a.flags & WG_X_STRIDE2) && wgrad_x_on_dy_grid(a) && a.sw >= 3 && a.shw >= 6 && a.H >= 8 && a.W >= 8 &&
          (a.M >= 16384 || (a.M >= 8192 && (a.Cin / 64) * (a.Cout / 64) >= 64)) &&   // small reductions go to the filter-row kernel unless the channel tiles alone fill the chip
          a.Cin % 64 == 0 && a.Cout % 64 == 0 && (a.M % 64 == 0) &&
          (long)a.N * a.Hx * a.Wx * a.Cin < (1L << 30) && (long)a.N * a.Hdy * a.Wdy * a.Cout < (1L << 30);
@@ -1697,7 +1704,7 @@ int gank_wgrad_dispatch(WgradArgs a, hipStream_t s) {
   const bool fast = (a.Cin % 8 == 0) && (a.Cout % 8 == 0);
   gank_prof_begin(1, flops, s, 2.0 * ((double)a.N * a.Hx * a.Wx * a.Cin + (double)a.N * a.Hdy * a.Wdy * a.Cout) + 4.0 * a.taps * a.Cin * a.Cout);
   int rc = -1;
-  const bool same_grid = (a.flags & (WG_X_STRIDE2 | GANK_IN_UPSAMPLE2X)) || (a.Hx == a.H && a.Wx == a.W);    // the lean kernel's plain gather assumes x on dy's grid
+  const bool same_grid = (a.flags & WG_X_STRIDE2) || wgrad_x_on_dy_grid(a);    // the lean kernel's plain and upsampled gathers bound their taps by dy's grid
   const bool dy_grid = (a.flags & GANK_DY_UPSAMPLE2X) || (a.Hdy == a.H && a.Wdy == a.W);
   const bool lean = fast && same_grid && dy_grid && a.sw >= 0 && a.shw >= 0 && (a.M % 64 == 0) &&
                     (long)a.N * a.Hx * a.Wx * a.Cin < (1L << 30) && (long)a.N * a.Hdy * a.Wdy * a.Cout < (1L << 30);
@@ -1714,7 +1721,7 @@ int gank_wgrad_dispatch(WgradArgs a, hipStream_t s) {
   // narrow operands: pack (tap, channel) into <= 32 MFMA columns so the wide operand streams once
   const bool plain = (a.flags == 0) && a.Hx == a.H && a.Wx == a.W && a.Hdy == a.H && a.Wdy == a.W &&      // the packed kernels walk x and dy on one grid
                      (long)a.M * (a.Cin > a.Cout ? a.Cin : a.Cout) < (1L << 30);
-  if (rc < 0 && plain && wgrad_narrow_stream_ok(a.N, a.H, a.W, a.Cin, a.Cout, a.ks)) {
+  if (rc < 0 && plain && a.pad == (a.ks - 1) / 2 && wgrad_narrow_stream_ok(a.N, a.H, a.W, a.Cin, a.Cout, a.ks)) {     // (the streaming kernel's pad is its filter's SAME pad)
     gank_prof_tag(1, a.ks == 3 ? "conv_wgrad_narrow_stream_kernel<3>" : "conv_wgrad_narrow_stream_kernel<1>");
     const NarrowWgArgs q = narrow_args(a.x, a.dy, a.dw, a.dbias, a.N, a.H, a.W, a.Cout, a.scale);
     rc = launch_wgrad_narrow_stream(q, a.ks, q, 0, s);
