@@ -4,7 +4,10 @@
 //   gank_prd_knn_partial     per row of a bank and per column segment the k smallest d2 to the OTHER rows of the bank;
 //   gank_prd_knn_finish      the segments of a row merged -> radii2 [n], the k-th smallest;
 //   gank_prd_counts_partial  per query row and column segment the number of bank rows j with d2_ij <= radii2[j], and min_j d2_ij;
-//   gank_prd_counts_finish   an int sum and a min over the segments.
+//   gank_prd_counts_finish   an int sum and a min over the segments;
+//   gank_prd_scores_partial  per query row and column segment max_j radii2[j] / d2_ij and the smallest radii2[j] among the balls
+//                            that hold the row (the realism and rarity scores of common/sample_scores.py), pruned balls left out;
+//   gank_prd_scores_finish   a max and a min over the segments.
 // d2_ij = (|a_i|^2 + |b_j|^2) - 2 <a_i, b_j> in float64 on float32 features (the widening is exact), clamped at 0.
 //
 // Decomposition.  A 256-thread workgroup owns a strip of 64 rows (blockIdx.x) and walks the 64-column tiles of one column
@@ -31,7 +34,11 @@
 //           padded with +inf.  A duplicated row is a neighbour at distance 0: nothing is excluded by value.
 //   counts: count += d2 <= radii2[column] (inclusive; the tile's 64 radii sit in LDS, -1 for columns >= n), nearest = min d2;
 //           the four classes add / min by xor shuffles -> part_count[row][segment], part_min[row][segment].
-// The k smallest of a set and an integer sum do not depend on the order or on the cut into segments; no atomics, no split of
+//   scores: a column with radii2 < 0 (pruned by the caller, or >= n: the -1 of the counts) is skipped.  Otherwise ratio =
+//           max(ratio, d2 == 0 ? +inf : radii2 / d2), one IEEE division (d2 == 0 also covers 0 / 0), from -inf; rare =
+//           min(rare, radii2) where d2 <= radii2, from +inf; max / min over the classes by xor shuffles -> part[row][segment],
+//           part2[row][segment].  The division runs after the accumulators have gone to LDS, on registers they have freed.
+// The k smallest of a set, an integer sum and a max / min do not depend on the order or on the cut into segments; no atomics, no split of
 // the contraction: two calls on the same data, with any segment counts, return the same bits.
 #include "f64_tile.h"
 
@@ -58,11 +65,15 @@ __device__ __forceinline__ void prd_insert(double (&best)[kPrdMaxK], double v) {
   }
 }
 
-// kRadii: a == b (the bank against itself), `part` = the k-lists.  Otherwise a = queries, b = bank, `part` = the minima.
-template <bool kRadii>
+enum PrdMode { kPrdRadii, kPrdCounts, kPrdScores };
+
+// kPrdRadii: a == b (the bank against itself), `part` = the k-lists.  Otherwise a = queries, b = bank; kPrdCounts: `part` = the
+// minima, `part_count` the counts; kPrdScores: `part` = the ratios, `part2` = the smallest holding radii.
+template <PrdMode kMode>
 __global__ __launch_bounds__(kPrdThreads) void prd_strip_kernel(const float* __restrict__ a, int na, const float* __restrict__ b, int nb, int D,
                                                                 const double* __restrict__ radii2, int k, int segments,
-                                                                double* __restrict__ part, int* __restrict__ part_count) {
+                                                                double* __restrict__ part, int* __restrict__ part_count,
+                                                                double* __restrict__ part2) {
   __shared__ __attribute__((aligned(16))) double buf[kF64StageDoubles];      // fs[side][row][k], then dots[row][col]
   __shared__ double norm[2][kPrdTile];
   __shared__ double rad[kPrdTile];
@@ -73,12 +84,14 @@ __global__ __launch_bounds__(kPrdThreads) void prd_strip_kernel(const float* __r
   const int c4 = (tid & 7) * 4;                       // staging item q: row (tid >> 3) + 32 q of the 128 staged rows, 4 features from c4
   const int srow = tid >> 2, cls = tid & 3;           // the epilogue's row and column class
   const int grow = bi * kPrdTile + srow;
+  constexpr bool kRadii = kMode == kPrdRadii;
 
   double best[kPrdMaxK];
 #pragma unroll
   for (int s = 0; s < kPrdMaxK; s++) best[s] = INFINITY;
   int count = 0;
   double nearest = INFINITY;
+  double ratio = -INFINITY, rare = INFINITY;
 
   for (int bj = t0; bj < t1; bj++) {
     const float* src[kF64Items];
@@ -133,10 +146,16 @@ __global__ __launch_bounds__(kPrdThreads) void prd_strip_kernel(const float* __r
       if (kRadii) {
         const double v = (col < nb && col != grow) ? d2 : INFINITY;       // self-exclusion by index
         if (v < best[kPrdMaxK - 1]) prd_insert(best, v);
-      } else {
+      } else if (kMode == kPrdCounts) {
         const double v = col < nb ? d2 : INFINITY;
         count += v <= rad[c] ? 1 : 0;
         nearest = fmin(nearest, v);
+      } else {
+        const double r2 = rad[c];
+        if (r2 >= 0.0) {                                // not pruned, and col < nb
+          ratio = fmax(ratio, d2 == 0.0 ? (double)INFINITY : r2 / d2);
+          if (d2 <= r2) rare = fmin(rare, r2);
+        }
       }
     }
     __syncthreads();                                  // the next tile stages over the dot products
@@ -158,7 +177,7 @@ __global__ __launch_bounds__(kPrdThreads) void prd_strip_kernel(const float* __r
       for (int s = 0; s < kPrdMaxK; s++)
         if (s < k) dst[s] = best[s];
     }
-  } else {
+  } else if (kMode == kPrdCounts) {
 #pragma unroll
     for (int o = 1; o <= 2; o <<= 1) {
       count += __shfl_xor(count, o, 64);
@@ -167,6 +186,16 @@ __global__ __launch_bounds__(kPrdThreads) void prd_strip_kernel(const float* __r
     if (cls == 0 && grow < na) {
       part_count[(size_t)grow * segments + seg] = count;
       part[(size_t)grow * segments + seg] = nearest;
+    }
+  } else {
+#pragma unroll
+    for (int o = 1; o <= 2; o <<= 1) {
+      ratio = fmax(ratio, __shfl_xor(ratio, o, 64));
+      rare = fmin(rare, __shfl_xor(rare, o, 64));
+    }
+    if (cls == 0 && grow < na) {
+      part[(size_t)grow * segments + seg] = ratio;
+      part2[(size_t)grow * segments + seg] = rare;
     }
   }
 }
@@ -206,6 +235,20 @@ __global__ __launch_bounds__(kPrdThreads) void prd_counts_finish_kernel(const in
   nearest2[i] = m;
 }
 
+__global__ __launch_bounds__(kPrdThreads) void prd_scores_finish_kernel(const double* __restrict__ part_ratio2, const double* __restrict__ part_rare2,
+                                                                        int nq, int segments, double* __restrict__ ratio2,
+                                                                        double* __restrict__ rare2) {
+  const int i = blockIdx.x * kPrdThreads + threadIdx.x;
+  if (i >= nq) return;
+  double hi = -INFINITY, lo = INFINITY;
+  for (int s = 0; s < segments; s++) {
+    hi = fmax(hi, part_ratio2[(size_t)i * segments + s]);
+    lo = fmin(lo, part_rare2[(size_t)i * segments + s]);
+  }
+  ratio2[i] = hi;
+  rare2[i] = lo;
+}
+
 int prd_check_shape(const char* what, int D, int segments, int columns) {
   GANK_REQUIRE(D >= 16 && D <= 4096 && D % 16 == 0, "%s: D = %d unsupported (a multiple of 16 in 16..4096)", what, D);
   GANK_REQUIRE(segments >= 1 && segments <= kPrdMaxSegments && segments <= prd_tiles(columns),
@@ -223,8 +266,8 @@ extern "C" int gank_prd_knn_partial(const float* x, int n, int D, int k, int seg
   if (prd_check_shape("prd_knn_partial", D, segments, n)) return 1;
   GANK_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)part & 7) == 0, "prd_knn_partial: misaligned pointer");
   const dim3 grid((unsigned)prd_tiles(n), (unsigned)segments);
-  hipLaunchKernelGGL(prd_strip_kernel<true>, grid, dim3(kPrdThreads), 0, (hipStream_t)stream, x, n, x, n, D, (const double*)nullptr, k, segments,
-                     part, (int*)nullptr);
+  hipLaunchKernelGGL(prd_strip_kernel<kPrdRadii>, grid, dim3(kPrdThreads), 0, (hipStream_t)stream, x, n, x, n, D, (const double*)nullptr, k, segments,
+                     part, (int*)nullptr, (double*)nullptr);
   GANK_LAUNCH_OK("prd_knn_partial");
   return 0;
 }
@@ -250,8 +293,8 @@ extern "C" int gank_prd_counts_partial(const float* q, int nq, const float* r, i
                    ((uintptr_t)part_min & 7) == 0,
                "prd_counts_partial: misaligned pointer");
   const dim3 grid((unsigned)prd_tiles(nq), (unsigned)segments);
-  hipLaunchKernelGGL(prd_strip_kernel<false>, grid, dim3(kPrdThreads), 0, (hipStream_t)stream, q, nq, r, nr, D, radii2, 0, segments, part_min,
-                     part_count);
+  hipLaunchKernelGGL(prd_strip_kernel<kPrdCounts>, grid, dim3(kPrdThreads), 0, (hipStream_t)stream, q, nq, r, nr, D, radii2, 0, segments, part_min,
+                     part_count, (double*)nullptr);
   GANK_LAUNCH_OK("prd_counts_partial");
   return 0;
 }
@@ -266,5 +309,33 @@ extern "C" int gank_prd_counts_finish(const int* part_count, const double* part_
   hipLaunchKernelGGL(prd_counts_finish_kernel, dim3((unsigned)cdiv(nq, kPrdThreads)), dim3(kPrdThreads), 0, (hipStream_t)stream, part_count,
                      part_min, nq, segments, count, nearest2);
   GANK_LAUNCH_OK("prd_counts_finish");
+  return 0;
+}
+
+extern "C" int gank_prd_scores_partial(const float* q, int nq, const float* r, int nr, int D, const double* radii2, int segments,
+                                       double* part_ratio2, double* part_rare2, void* stream) {
+  GANK_REQUIRE(q && r && radii2 && part_ratio2 && part_rare2, "prd_scores_partial: null pointer");
+  GANK_REQUIRE(nq >= 1 && nq <= kPrdMaxRows && nr >= 1 && nr <= kPrdMaxRows, "prd_scores_partial: nq = %d, nr = %d (1..%d)", nq, nr, kPrdMaxRows);
+  if (prd_check_shape("prd_scores_partial", D, segments, nr)) return 1;
+  GANK_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)r & 15) == 0 && ((uintptr_t)radii2 & 7) == 0 && ((uintptr_t)part_ratio2 & 7) == 0 &&
+                   ((uintptr_t)part_rare2 & 7) == 0,
+               "prd_scores_partial: misaligned pointer");
+  const dim3 grid((unsigned)prd_tiles(nq), (unsigned)segments);
+  hipLaunchKernelGGL(prd_strip_kernel<kPrdScores>, grid, dim3(kPrdThreads), 0, (hipStream_t)stream, q, nq, r, nr, D, radii2, 0, segments,
+                     part_ratio2, (int*)nullptr, part_rare2);
+  GANK_LAUNCH_OK("prd_scores_partial");
+  return 0;
+}
+
+extern "C" int gank_prd_scores_finish(const double* part_ratio2, const double* part_rare2, int nq, int segments, double* ratio2, double* rare2,
+                                      void* stream) {
+  GANK_REQUIRE(part_ratio2 && part_rare2 && ratio2 && rare2, "prd_scores_finish: null pointer");
+  GANK_REQUIRE(nq >= 1 && nq <= kPrdMaxRows, "prd_scores_finish: nq = %d (1..%d)", nq, kPrdMaxRows);
+  GANK_REQUIRE(segments >= 1 && segments <= kPrdMaxSegments, "prd_scores_finish: segments = %d (1..%d)", segments, kPrdMaxSegments);
+  GANK_REQUIRE(((uintptr_t)part_ratio2 & 7) == 0 && ((uintptr_t)part_rare2 & 7) == 0 && ((uintptr_t)ratio2 & 7) == 0 && ((uintptr_t)rare2 & 7) == 0,
+               "prd_scores_finish: misaligned pointer");
+  hipLaunchKernelGGL(prd_scores_finish_kernel, dim3((unsigned)cdiv(nq, kPrdThreads)), dim3(kPrdThreads), 0, (hipStream_t)stream, part_ratio2,
+                     part_rare2, nq, segments, ratio2, rare2);
+  GANK_LAUNCH_OK("prd_scores_finish");
   return 0;
 }

@@ -2154,6 +2154,31 @@ def prd_manifold_counts(q, r, radii2, segments=None, partial=None, counts=None, 
     return counts.view(-1)[:nq], nearest.view(-1)[:nq]
 
 
+def prd_sample_scores(q, r, radii2, segments=None):
+    """Queries q float32 [nq, D], a bank r float32 [nr, D] and its squared radii float64 [nr] (`prd_knn_radii`; a row with
+    radii2 < 0 is pruned: it takes part in neither result) -> (ratio2, rare2), float64 [nq] each, on the device: per query row
+    max_j radii2[j] / d2(q_i, r_j) (+inf where a d2 is 0, -inf when every row is pruned) and the smallest radii2[j] among the
+    bank rows with d2(q_i, r_j) <= radii2[j] (inclusive; +inf when no ball holds the row), in float64 (gank_prd_scores_partial,
+    gank_prd_scores_finish).  segments: the cut of the bank (prd_default_segments(nr, nq) when None); the result does not
+    depend on it."""
+    _prd_features("prd_sample_scores", q=q, r=r)
+    if q.shape[1] != r.shape[1]:
+        raise RuntimeError(f"gank: prd_sample_scores: q {tuple(q.shape)} and r {tuple(r.shape)} differ in the feature width")
+    nq, nr = q.shape[0], r.shape[0]
+    if not radii2.is_cuda or radii2.dtype != torch.float64 or tuple(radii2.shape) != (nr,):
+        raise RuntimeError(f"gank: prd_sample_scores takes radii2 float64 [{nr}] on the GPU, got {tuple(radii2.shape)} {radii2.dtype}")
+    segments = prd_default_segments(nr, nq) if segments is None else int(segments)
+    m = nq * max(segments, 0)
+    part = torch.empty((2, max(m, 1)), dtype=torch.float64, device=q.device)      # the ratios, then the smallest holding radii
+    out = torch.empty((2, max(nq, 1)), dtype=torch.float64, device=q.device)
+    _lib.check(lib().gank_prd_scores_partial(_p(q, F32, "q"), nq, _p(r, F32, "r"), nr, q.shape[1], _p(radii2, torch.float64, "radii2"),
+                                             segments, _p(part[0], torch.float64, "part"), _p(part[1], torch.float64, "part"), _stream()),
+               "prd_sample_scores")
+    _lib.check(lib().gank_prd_scores_finish(_p(part[0], torch.float64, "part"), _p(part[1], torch.float64, "part"), nq, segments,
+                                            _p(out[0], torch.float64, "out"), _p(out[1], torch.float64, "out"), _stream()), "prd_scores_finish")
+    return out[0, :nq], out[1, :nq]
+
+
 # ------------------------------------------------------------------ sliced Wasserstein distance (common/swd.py)
 F64 = torch.float64
 

@@ -87,6 +87,24 @@ class SampleMetrics:
         return calculate_prdc(real, sample_features(self._metric_draw(), n, net), net, k)
 
     @torch.no_grad()
+    def sample_scores(self, real, n=10000, net=None, k=3, prune=0.5):
+        """Per-sample realism and rarity scores (common/sample_scores.py: which samples lie deep in the k-NN manifold of the real
+        pool_3 features, and which in its sparse regions) of n samples against `real`, drawn and batched as for
+        `precision_recall` -> the dict of `calculate_sample_scores` (realism, rarity, inside [n] and their summary scalars)
+        plus `samples`: the n drawn images, uint8 [n,H,W,3] on the device, row i the sample of score i -- index them with
+        `sample_scores.rank_samples` for a sheet of the best and the worst."""
+        from .common.kid import sample_features
+        from .common.sample_scores import calculate_sample_scores
+        draw, drawn = self._metric_draw(), []
+
+        def keep():
+            drawn.append(draw())
+            return drawn[-1]
+        out = calculate_sample_scores(real, sample_features(keep, n, net), net, k, prune)
+        out['samples'] = torch.cat(drawn)[:n]           # the last pass is cut to the rows that were scored
+        return out
+
+    @torch.no_grad()
     def swd(self, real, n=8192, seed=0, **kw):
         """Sliced Wasserstein distance on Laplacian-pyramid patches (common/swd.py; Karras et al. 2018, section 5: no network,
         no downloaded weights) between n samples and the first n images of `real` [N >= n,H,W,3] at the samples' size (uint8 or

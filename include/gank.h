@@ -979,6 +979,16 @@ int gank_kid_finish(const double* partial, int subsets, int m, double* out, void
  *   part_count int32 [nq][segments] = the number of the segment's columns j with d2_ij <= radii2[j] (inclusive) and
  *   part_min float64 [nq][segments] = their smallest d2_ij.  No self-exclusion.
  * gank_prd_counts_finish: count int32 [nq] = the sum, nearest2 float64 [nq] = the minimum over the segments.
+ * gank_prd_scores_partial: the per-sample scores of common/sample_scores.py (the realism score of Kynkaanniemi et al.,
+ *   section 5; Han et al., "Rarity Score: A New Metric to Evaluate the Uncommonness of Synthesized Images").  q, r, radii2 as
+ *   for the counts; a bank row with radii2[j] < 0 is PRUNED and takes part in neither output.  Per query row and segment,
+ *   over the segment's unpruned columns j: part_ratio2 float64 [nq][segments] = max_j radii2[j] / d2_ij, one IEEE division a
+ *   pair, +inf where d2_ij == 0 (also when radii2[j] == 0), -inf when the segment holds no unpruned column; part_rare2
+ *   float64 [nq][segments] = the smallest radii2[j] among the j with d2_ij <= radii2[j] (inclusive, as the counts), +inf when
+ *   no ball of the segment holds the row.  No self-exclusion; every entry is written by one plain store.  A NaN in radii2 is
+ *   the caller's error.
+ * gank_prd_scores_finish: ratio2 float64 [nq] = the maximum of part_ratio2, rare2 float64 [nq] = the minimum of part_rare2
+ *   over the segments: values only, no neighbour indices.
  *   Refused: null pointers; D % 16 != 0 or D outside 16..4096 (the rule of gank_kid_block_sums); k outside 1..8; n < k + 1;
  *   nq < 1, nr < 1; more than 2^24 rows a side; segments < 1, > 65535 or more than the column tiles; features not 16-byte
  *   aligned. */
@@ -987,6 +997,10 @@ int gank_prd_knn_finish(const double* part, int n, int k, int segments, double* 
 int gank_prd_counts_partial(const float* q, int nq, const float* r, int nr, int D, const double* radii2, int segments, int* part_count,
                             double* part_min, void* stream);
 int gank_prd_counts_finish(const int* part_count, const double* part_min, int nq, int segments, int* count, double* nearest2, void* stream);
+int gank_prd_scores_partial(const float* q, int nq, const float* r, int nr, int D, const double* radii2, int segments, double* part_ratio2,
+                            double* part_rare2, void* stream);
+int gank_prd_scores_finish(const double* part_ratio2, const double* part_rare2, int nq, int segments, double* ratio2, double* rare2,
+                           void* stream);
 
 /* ---- Sliced Wasserstein distance on Laplacian-pyramid patches (common/swd.py; Karras et al., "Progressive Growing of GANs for
  * Improved Quality, Stability, and Variation", section 5) -------------------------------------------------------------------
