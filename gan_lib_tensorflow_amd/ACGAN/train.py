@@ -5,6 +5,7 @@ One step (train.py:194-204) = 1 generator update (skipped at step 0) + n_dis = 5
                    + 10 * mean((||grad_x D(x_hat)||_2 - 1)^2),  x_hat = real + alpha (fake - real)   (:99-107)
                    + mean softmax cross-entropy of the class head on the real batch          (:111-114)
     generator loss = -mean(D(G(z))) + acgan_scale_G * cross-entropy of the class head on the fakes (:117-121)
+(the second term is the default of `ACGANTrainer(penalty=...)`: PENALTIES below has the one-sided, DRAGAN, R1 and R2 terms and 'none')
 both with tf.train.AdamOptimizer(beta1=0, beta2=0.9) at a learning rate that decays linearly from 4e-4 to 2e-4 over
 max_iter / 2 generator steps (tf.train.polynomial_decay on `global_step`, :141-148).
 
@@ -12,6 +13,9 @@ Data parallel (config 3: global batch 256 over 8 GPUs): one process per GPU, eac
 samples and its own batch-norm statistics (as the reference's towers would have); flat gradient buffers summed with one
 RCCL all-reduce per update, 1/world applied inside the Adam kernel.
 """
+import numbers
+
+import numpy as np
 import torch
 
 from .. import functional as Fn
@@ -46,11 +50,45 @@ def _g_prep_kind(name, W):
     return 0
 
 
+# The critic's gradient regulariser: penalty -> (the function of the slope, kernels.GRAD_PENALTY_KINDS; the penalised point)
+PENALTIES = {
+    'wgan-gp': ('two_sided', 'interpolates'),     # Gulrajani et al. 2017: the reference's term (train.py:99-107)
+    'wgan-lp': ('one_sided', 'interpolates'),     # Petzka et al. 2018
+    'dragan': ('two_sided', 'perturbed'),         # Kodali et al. 2017: real + 0.5 * std(real) * U[0, 1)
+    'r1': ('squared', 'real'),                    # Mescheder et al. 2018; penalty_weight = gamma / 2
+    'r2': ('squared', 'fake'),
+    'none': (None, None),
+}
+
+
+def check_penalty(penalty, penalty_weight, penalty_every):
+    """the constructor's checks, before any device work"""
+    if penalty not in PENALTIES:
+        raise ValueError(f"penalty {penalty!r}: one of {', '.join(PENALTIES)}")
+    if isinstance(penalty_every, bool) or not isinstance(penalty_every, numbers.Real) or int(penalty_every) != penalty_every or penalty_every < 1:
+        raise ValueError(f"penalty_every {penalty_every!r}: a whole number of critic updates, at least 1")
+    if penalty != 'none' and (isinstance(penalty_weight, bool) or not isinstance(penalty_weight, numbers.Real) or not penalty_weight > 0):
+        raise ValueError(f"penalty_weight {penalty_weight!r} with penalty {penalty!r}: a positive weight (penalty='none' switches the term off)")
+
+
 class ACGANTrainer(trainer.SampleMetrics, trainer.GraphTrainer):
     def __init__(self, batch_size=64, z_dim=128, acgan_scale_G=0.1, n_dis=5, max_iter=100000, device="cuda", seed=0,
-                 process_group=None, state=None, use_graphs=True, allow_eager_fallback=False):
+                 process_group=None, state=None, use_graphs=True, allow_eager_fallback=False, penalty='wgan-gp', penalty_weight=10.0,
+                 penalty_every=1):
+        """penalty: the critic's gradient regulariser (PENALTIES), `penalty_weight` its weight.  penalty_every = k > 1 is the lazy
+        regularisation of StyleGAN2 (Karras et al. 2020, appendix B): the term is added on the critic updates whose count is a
+        multiple of k, with weight k * penalty_weight; the others run the 'none' form.  `state` may be a `state_dict()` of this
+        trainer: the variables and the count of critic updates."""
+        check_penalty(penalty, penalty_weight, penalty_every)
         super().__init__(device, seed, process_group, use_graphs, allow_eager_fallback)
         self.batch, self.z_dim, self.scale_g, self.n_dis, self.max_iter = batch_size, z_dim, acgan_scale_G, n_dis, max_iter
+        self.penalty, self.penalty_every = penalty, int(penalty_every)
+        self.penalty_weight = float(penalty_weight) if isinstance(penalty_weight, numbers.Real) else 0.0      # ('none' asks for no weight)
+        self.d_updates = 0               # critic updates taken: chooses the form of the next one on the host, outside any capture
+        self._d_losses = {}              # graph key -> the loss tensors that form of the critic update writes
+        if state is not None and '_d_updates' in state:
+            state = dict(state)
+            self.d_updates = int(state.pop('_d_updates'))
         self.model = ACGAN()
         self.global_step = 0
         # build once (variables are created by name on first use)
@@ -90,27 +128,47 @@ class ACGANTrainer(trainer.SampleMetrics, trainer.GraphTrainer):
         return polynomial_decay(self.global_step, decay_steps=self.max_iter // 2)
 
     # ---- the two losses (eager; explicit inputs override the device RNG for parity tests) -----------------------------
-    def d_loss(self, real, real_labels, z=None, fake_labels=None, alpha=None):
+    def d_loss(self, real, real_labels, z=None, fake_labels=None, alpha=None, u=None, penalise=True):
+        """penalise=False: the form of an update that carries no penalty (`penalty='none'`, and the updates lazy regularisation skips)"""
         set_default_store(self.store)
         b = real.shape[0]
         m = self.model
+        kind, point = PENALTIES[self.penalty if penalise else 'none']
         if z is None:
             z = K.rng_normal((b, self.z_dim), self.rng_state)
         if fake_labels is None:
             fake_labels = K.rng_labels(b, 10, self.rng_state)
-        if alpha is None:
+        if alpha is None and point == 'interpolates':
             alpha = K.rng_uniform(b, self.rng_state)
+        if u is None and point == 'perturbed':
+            u = K.rng_uniform(real.numel(), self.rng_state)
         with torch.no_grad():            # d_train_op differentiates w.r.t. d_vars only (train.py:148)
             x_fake = m.get_generator(z, fake_labels)
         disc_real, ac_real = m.get_discriminator(real, real_labels, update_collection=None)
         disc_fake, _ = m.get_discriminator(x_fake, fake_labels, update_collection='NO_OPS', reuse=True)
         d_gan = Fn.hinge_d_loss(Fn.concat_rows(disc_real, disc_fake), b)
-        interp = K.lerp_rows(real, x_fake, alpha).requires_grad_(True)
-        d_int, _ = m.get_discriminator(interp, real_labels, 'NO_OPS', reuse=True)
+        if kind is None:
+            d_ac = Fn.softmax_xent(ac_real, real_labels)
+            self.losses.update(d_loss_gan=d_gan.detach(), d_loss_acgan=d_ac.detach(), gradient_penalty=Fn.constant_like(d_gan.detach(), 0.0))
+            return Fn.weighted_sum([d_gan, d_ac])
+        # the penalised point: a third pass over the critic, differentiated twice
+        if point == 'interpolates':
+            x_pen, pen_labels = K.lerp_rows(real, x_fake, alpha), real_labels
+        elif point == 'perturbed':
+            x_pen, pen_labels = K.dragan_perturb(real, u), real_labels
+        elif point == 'real':
+            x_pen, pen_labels = real.detach(), real_labels           # (an alias: `real` itself stays without a gradient)
+        else:
+            x_pen, pen_labels = x_fake.detach(), fake_labels         # detached from the generator (it was run without a graph)
+        interp = x_pen.requires_grad_(True)
+        d_int, _ = m.get_discriminator(interp, pen_labels, 'NO_OPS', reuse=True)
         ones = Fn.constant_like(d_int, 1.0)                 # tf.gradients(D(x_hat), [x_hat]): d(sum of logits)/d(x_hat); a persistent buffer
         with F2.input_gradient_only():       # the filter / bias / table gradients of this pass are not part of the penalty
             (grads,) = torch.autograd.grad([d_int], [interp], [ones], create_graph=True)
-        gp = F2.gradient_penalty(grads, 10.0)
+        if self.penalty == 'wgan-gp':
+            gp = F2.gradient_penalty(grads, self.penalty_weight * self.penalty_every)      # the reference's term, on its own kernel
+        else:
+            gp = F2.gradient_penalty(grads, self.penalty_weight * self.penalty_every, kind, 1.0)
         d_ac = Fn.softmax_xent(ac_real, real_labels)
         self.losses.update(d_loss_gan=K.weighted_sum_f32([d_gan.detach(), gp.detach()], [1.0, 1.0]), d_loss_acgan=d_ac.detach(), gradient_penalty=gp.detach())
         return Fn.weighted_sum([d_gan, gp, d_ac])
@@ -133,15 +191,20 @@ class ACGANTrainer(trainer.SampleMetrics, trainer.GraphTrainer):
         return total
 
     # ---- updates --------------------------------------------------------------------------------------------------
-    def _d_fwd_bwd(self):
+    def _d_fwd_bwd(self, penalise=True):
         with F2.one_update():            # every pass over the critic in this update shares one preparation of its weights
             if BATCHED_PREP:
                 F2.prepare_batched(self.d_params)
             real = K.preprocess_real(self.real_u8, self.rng_state)         # [B, 32, 32, 3] bf16   (train.py:80-83)
             K.zero_(self.d_flat['grads'])
-            loss = self.d_loss(real, self.real_labels)
+            loss = self.d_loss(real, self.real_labels, penalise=penalise)
             loss.backward(gradient=Fn.unit_seed(loss))
             self.losses['d_loss'] = loss.detach()
+        # (runs on the eager and on the capturing call of a form, not on a replay: d_step puts these back after every update)
+        self._d_losses['d' if penalise else 'd_plain'] = {k: self.losses[k] for k in ('d_loss', 'd_loss_gan', 'd_loss_acgan', 'gradient_penalty')}
+
+    def _d_fwd_bwd_plain(self):
+        self._d_fwd_bwd(penalise=False)
 
     def _g_fwd_bwd(self):
         with F2.one_update():
@@ -153,11 +216,26 @@ class ACGANTrainer(trainer.SampleMetrics, trainer.GraphTrainer):
             self.losses['g_loss'] = loss.detach()
 
     def d_step(self, real_u8, labels):
-        """one critic update on a uint8 [B, 3072] CHW-planar batch + int labels (train.py:199-204)"""
+        """one critic update on a uint8 [B, 3072] CHW-planar batch + int labels (train.py:199-204).  Two forms, each a captured graph
+        of its own: 'd' carries the penalty, 'd_plain' does not (penalty='none'; under lazy regularisation every update whose count
+        is no multiple of penalty_every).  The count lives on the host and picks the form outside any capture."""
         self.real_u8.copy_(real_u8, non_blocking=True)
         self.real_labels.copy_(labels, non_blocking=True)
-        self._update('d', self._d_fwd_bwd, self.d_opt)
+        penalise = self.penalty != 'none' and self.d_updates % self.penalty_every == 0
+        key = 'd' if penalise else 'd_plain'
+        self._update(key, self._d_fwd_bwd if penalise else self._d_fwd_bwd_plain, self.d_opt)
+        self.d_updates += 1
+        self.losses.update(self._d_losses[key])          # a replay wrote the tensors of ITS form, whichever form ran last in Python
         return self.losses['d_loss']
+
+    def state_dict(self):
+        """the variables by name (`store.state_dict()`) and `_d_updates`, the count of critic updates that schedules the lazy penalty;
+        the constructor's `state` takes it back.  Not a full checkpoint: `global_step` (the learning-rate decay), the Adam moments and
+        step counts and the RNG state are not in it, so a trainer rebuilt from it keeps its weights and the penalty schedule and starts
+        those afresh."""
+        sd = self.store.state_dict()
+        sd['_d_updates'] = np.asarray(self.d_updates, dtype=np.int64)
+        return sd
 
     def g_step(self):
         self._update('g', self._g_fwd_bwd, self.g_opt)

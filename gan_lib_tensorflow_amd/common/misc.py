@@ -31,9 +31,13 @@ def get_loss(disc_real, disc_fake, loss_type='HINGE'):
     raise NotImplementedError('loss_type %r (misc.py:310-394 knows HINGE, WGAN, WGAN-GP, LSGAN, CGAN, Modified_MiniMax, MiniMax)' % (loss_type,))
 
 
-def gradient_penalty(gradients, weight=10.0):
+def gradient_penalty(gradients, weight=10.0, kind='two_sided', target=1.0):
     """weight * mean((sqrt(sum(g^2, axis=[1,2,3]) + 1e-10) - 1)^2)  -- the block the reference asks to paste at the call
     site (misc.py:341-349; ACGAN/train.py:104-106).  `gradients` must come from a critic built of `functional2` operators
-    with create_graph=True so the penalty can be differentiated with respect to the critic's weights."""
+    with create_graph=True so the penalty can be differentiated with respect to the critic's weights.
+    With s = sqrt(sum(g^2) + 1e-10) per sample, `kind` selects the function of the slope, the caller the penalised point:
+      'two_sided'  weight * mean((s - target)^2)          WGAN-GP at the interpolates; DRAGAN at real + 0.5 * std(real) * U[0, 1)
+      'one_sided'  weight * mean(max(0, s - target)^2)    WGAN-LP at the interpolates
+      'squared'    weight * mean(sum(g^2))                R1 at the real batch, R2 at the generated one; weight = gamma / 2"""
     from .. import functional2 as F2
-    return F2.gradient_penalty(gradients, weight)
+    return F2.gradient_penalty(gradients, weight, kind, target)

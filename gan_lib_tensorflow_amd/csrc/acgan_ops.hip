@@ -3,7 +3,8 @@
 //     gradient with respect to the critic's weights, ACGAN/train.py:99-107: every op of the critic is differentiated
 //     twice; conv / dense / pooling / leaky-relu compose from their own first-order kernels, batch norm does not);
 //   * the moving-statistics update of tf.contrib.layers.batch_norm (common/ops/normalization.py:8-24) as one launch;
-//   * the gradient-penalty reduction, the real/fake interpolation, spatial mean and its adjoint, uniform random numbers.
+//   * the gradient-penalty reduction, the real/fake interpolation, spatial mean and its adjoint, uniform random numbers;
+//   * the penalties beside WGAN-GP on the same double backward (one-sided, squared norm, any target) and DRAGAN's perturbed point.
 // All HBM / latency bound; 16 bytes per lane where the shape allows.
 #include "gank_common.h"
 
@@ -189,6 +190,176 @@ extern "C" int gank_gp_loss(const void* grad, float* loss, void* dgrad, float* w
   hipLaunchKernelGGL(gp_rows_kernel, dim3(N), dim3(256), 0, s, (const bf16*)grad, ws, (float*)dgrad, N, D, lambda);
   hipLaunchKernelGGL(sum_small_kernel, dim3(1), dim3(256), 0, s, ws, loss, N);
   GANK_LAUNCH_OK("gp_loss");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The gradient penalties beside WGAN-GP (the family misc.py:337-352 leaves to the call site).  With
+// s_n = sqrt(sum_d g[n,d]^2 + 1e-10):
+//   kind 0  two-sided   lambda * mean_n (s_n - target)^2            (Gulrajani et al. 2017; DRAGAN, Kodali et al. 2017)
+//   kind 1  one-sided   lambda * mean_n max(0, s_n - target)^2      (WGAN-LP, Petzka et al. 2018): a row at or below the target
+//                       contributes exactly 0 and has dgrad exactly 0
+//   kind 2  squared     lambda * mean_n sum_d g[n,d]^2              (R1 / R2, Mescheder et al. 2018): no square root, no epsilon,
+//                       dgrad = 2 lambda / N * g, so a zero gradient has derivative 0 and not 0/0
+// One block per row.  A row of D % 8 == 0, D <= 4096 elements (the trainer's 3072: 384 vectors of 8 on 256 threads) is read once
+// into registers, 16 bytes per lane, and dgrad is written from them; any other row takes the looped path, which reads it twice.
+// fp32 accumulation in a fixed order (thread-serial, xor butterfly, wave order), no atomics; sum_small_kernel takes the mean.
+// ---------------------------------------------------------------------------------------------------------------
+#define GPEN_VEC 2                      // 8-element vectors a thread holds on the resident path: rows up to 256 * 8 * GPEN_VEC
+
+__device__ __forceinline__ float gpen_row_term(float tot, float lambda, float target, int kind, int N, float* pen) {
+  // -> k with dgrad = k * g; *pen = this row's share of the loss
+  if (kind == 2) {
+    *pen = lambda * tot / (float)N;
+    return 2.f * lambda / (float)N;
+  }
+  const float slope = sqrtf(tot + 1e-10f);
+  const float e = slope - target;
+  if (kind == 1 && !(e > 0.f)) {
+    *pen = 0.f;
+    return 0.f;
+  }
+  *pen = lambda * e * e / (float)N;
+  return lambda * 2.f * e / (slope * (float)N);
+}
+
+template <bool RESIDENT>
+__global__ __launch_bounds__(256) void grad_penalty_rows_kernel(const bf16* __restrict__ g, float* __restrict__ pen, float* __restrict__ dg, int N, long D,
+                                                                float lambda, float target, int kind) {
+  __shared__ float red[16];
+  const bf16* row = g + (long)blockIdx.x * D;
+  float* drow = dg + (long)blockIdx.x * D;
+  float acc = 0.f, p = 0.f;
+  if (RESIDENT) {                       // D % 8 == 0, D <= 2048 * GPEN_VEC, both rows 16-byte aligned (checked by the caller)
+    const int nvec = (int)(D >> 3);
+    bf16x8 v[GPEN_VEC];
+#pragma unroll
+    for (int j = 0; j < GPEN_VEC; j++) {
+      const int iv = j * 256 + threadIdx.x;
+      if (iv < nvec) {
+        v[j] = *reinterpret_cast<const bf16x8*>(row + (long)iv * 8);
+#pragma unroll
+        for (int e = 0; e < 8; e++) { const float f = bf2f(v[j][e]); acc += f * f; }
+      }
+    }
+    const float k = gpen_row_term(block_sum(acc, red), lambda, target, kind, N, &p);
+#pragma unroll
+    for (int j = 0; j < GPEN_VEC; j++) {
+      const int iv = j * 256 + threadIdx.x;
+      if (iv < nvec) {
+        f32x4 lo, hi;
+#pragma unroll
+        for (int e = 0; e < 4; e++) { lo[e] = k * bf2f(v[j][e]); hi[e] = k * bf2f(v[j][4 + e]); }
+        *reinterpret_cast<f32x4*>(drow + (long)iv * 8) = lo;
+        *reinterpret_cast<f32x4*>(drow + (long)iv * 8 + 4) = hi;
+      }
+    }
+  } else {
+    for (long i = threadIdx.x; i < D; i += 256) { const float f = bf2f(row[i]); acc += f * f; }
+    const float k = gpen_row_term(block_sum(acc, red), lambda, target, kind, N, &p);
+    for (long i = threadIdx.x; i < D; i += 256) drow[i] = k * bf2f(row[i]);
+  }
+  if (threadIdx.x == 0) pen[blockIdx.x] = p;
+}
+
+extern "C" int gank_grad_penalty(const void* grad, float* loss, void* dgrad, float* ws, int N, long D, float lambda, float target, int kind,
+                                 void* stream) {
+  GANK_REQUIRE(grad && loss && dgrad && ws && N > 0 && D > 0, "grad_penalty: bad arguments");
+  GANK_REQUIRE(kind >= 0 && kind <= 2, "grad_penalty: kind %d (0 two-sided, 1 one-sided, 2 squared norm)", kind);
+  hipStream_t s = (hipStream_t)stream;
+  const bool resident = D % 8 == 0 && D <= 2048L * GPEN_VEC && ((size_t)grad & 15) == 0 && ((size_t)dgrad & 15) == 0;
+  if (resident)
+    hipLaunchKernelGGL(grad_penalty_rows_kernel<true>, dim3(N), dim3(256), 0, s, (const bf16*)grad, ws, (float*)dgrad, N, D, lambda, target, kind);
+  else
+    hipLaunchKernelGGL(grad_penalty_rows_kernel<false>, dim3(N), dim3(256), 0, s, (const bf16*)grad, ws, (float*)dgrad, N, D, lambda, target, kind);
+  hipLaunchKernelGGL(sum_small_kernel, dim3(1), dim3(256), 0, s, ws, loss, N);
+  GANK_LAUNCH_OK("grad_penalty");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// DRAGAN's penalised point (Kodali et al. 2017): out = real + 0.5 * sigma * u, sigma = the population standard deviation of
+// ALL elements of real (x.std() of the original), u in [0, 1) one per element.  sigma never leaves the device:
+//   1. block b sums (x - x0) and (x - x0)^2 over its DRAGAN_CHUNK elements in fp32 (x0 = real[0]: the variance does not see
+//      the shift, a constant image sums exact zeros, and an image that is nearly constant no longer cancels in E[x^2] - E[x]^2)
+//      -> ws[2b], ws[2b + 1]; thread-serial, xor butterfly, wave order: fixed;
+//   2. one block adds the partials in double in a fixed order, forms the variance in double -> ws[2 * parts] = sigma;
+//   3. out = bf16(real + 0.5 * sigma * u), one rounding; where the perturbation is zero `real` passes through to the bit.
+// ---------------------------------------------------------------------------------------------------------------
+#define DRAGAN_CHUNK 4096               // elements per fp32 partial: 256 threads x 2 vectors of 8
+
+__global__ __launch_bounds__(256) void dragan_partials_kernel(const bf16* __restrict__ x, float* __restrict__ ws, long total) {
+  __shared__ float red[16];
+  const float x0 = bf2f(x[0]);
+  const long c0 = (long)blockIdx.x * DRAGAN_CHUNK;
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < DRAGAN_CHUNK / 2048; j++) {
+    const long i = c0 + (long)(j * 256 + threadIdx.x) * 8;
+    if (i + 8 <= total) {
+      const bf16x8 v = *reinterpret_cast<const bf16x8*>(x + i);
+#pragma unroll
+      for (int e = 0; e < 8; e++) { const float d = bf2f(v[e]) - x0; s1 += d; s2 += d * d; }
+    } else {
+      for (long q = i; q < total; q++) { const float d = bf2f(x[q]) - x0; s1 += d; s2 += d * d; }
+    }
+  }
+  s1 = block_sum(s1, red);
+  s2 = block_sum(s2, red);
+  if (threadIdx.x == 0) { ws[2 * (long)blockIdx.x] = s1; ws[2 * (long)blockIdx.x + 1] = s2; }
+}
+
+__global__ __launch_bounds__(256) void dragan_sigma_kernel(float* __restrict__ ws, long parts, long total) {
+  __shared__ double r1[256], r2[256];
+  double a = 0.0, b = 0.0;
+  for (long i = threadIdx.x; i < parts; i += 256) { a += (double)ws[2 * i]; b += (double)ws[2 * i + 1]; }
+  r1[threadIdx.x] = a;
+  r2[threadIdx.x] = b;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t1 = 0.0, t2 = 0.0;
+    for (int i = 0; i < 256; i++) { t1 += r1[i]; t2 += r2[i]; }
+    const double m = t1 / (double)total;
+    const double var = t2 / (double)total - m * m;
+    ws[2 * parts] = var > 0.0 ? (float)sqrt(var) : 0.f;
+  }
+}
+
+__global__ void dragan_apply_kernel(const bf16* __restrict__ x, const float* __restrict__ u, const float* __restrict__ sigma, bf16* __restrict__ out,
+                                    long total) {
+  const float hs = 0.5f * sigma[0];
+  const long nvec = total >> 3;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
+    const bf16x8 v = *reinterpret_cast<const bf16x8*>(x + i * 8);
+    const f32x4 ua = *reinterpret_cast<const f32x4*>(u + i * 8), ub = *reinterpret_cast<const f32x4*>(u + i * 8 + 4);
+    bf16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+      const float d = hs * (e < 4 ? ua[e] : ub[e - 4]);
+      o[e] = d == 0.f ? v[e] : f2bf(bf2f(v[e]) + d);
+    }
+    *reinterpret_cast<bf16x8*>(out + i * 8) = o;
+  }
+  if (blockIdx.x == 0)
+    for (long i = nvec * 8 + threadIdx.x; i < total; i += blockDim.x) {
+      const float d = hs * u[i];
+      out[i] = d == 0.f ? x[i] : f2bf(bf2f(x[i]) + d);
+    }
+}
+
+extern "C" int gank_dragan_perturb(const void* real, const float* u, void* out, float* ws, long total, void* stream) {
+  GANK_REQUIRE(real && u && out && ws && total > 0, "dragan_perturb: bad arguments");
+  GANK_REQUIRE(((size_t)real & 15) == 0 && ((size_t)u & 15) == 0 && ((size_t)out & 15) == 0, "dragan_perturb: real, u and out must be 16-byte aligned");
+  const long parts = (total + DRAGAN_CHUNK - 1) / DRAGAN_CHUNK;
+  GANK_REQUIRE(parts <= 0x7fffffffL, "dragan_perturb: %ld elements are more than one grid of partials holds", total);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(dragan_partials_kernel, dim3((unsigned)parts), dim3(256), 0, s, (const bf16*)real, ws, total);
+  hipLaunchKernelGGL(dragan_sigma_kernel, dim3(1), dim3(256), 0, s, ws, parts, total);
+  long blocks = ((total >> 3) + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(dragan_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16*)real, u, ws + 2 * parts, (bf16*)out, total);
+  GANK_LAUNCH_OK("dragan_perturb");
   return 0;
 }
 

@@ -475,6 +475,22 @@ class GPLoss(Function):
         return K.loss_grad_scale(dg32, _c(g.to(torch.float32)).reshape(1)), None       # fp32 product, one rounding to bf16
 
 
+class GradPenalty(Function):
+    """The penalties beside GPLoss (kernels.grad_penalty): lambda * mean_n of (s_n - target)^2, max(0, s_n - target)^2 or
+    sum_d g^2 -- DRAGAN / WGAN-LP / R1 and R2.  Backward as GPLoss: the saved fp32 derivative times the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, grad, lam, target, kind):
+        loss, dg = K.grad_penalty(_c(grad), lam, target, kind)
+        ctx.save_for_backward(dg)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dg32,) = ctx.saved_tensors
+        return K.loss_grad_scale(dg32, _c(g.to(torch.float32)).reshape(1)), None, None, None
+
+
 # ---- functional forms -------------------------------------------------------------------------------------------
 class AddF(Function):
     """a + b (one launch); linear, so its backward is differentiable as it stands"""
@@ -542,5 +558,9 @@ def batch_norm_train(x, gamma, beta):
     return BNF.apply(x, gamma, beta)
 
 
-def gradient_penalty(grad, lam=10.0):
-    return GPLoss.apply(grad, lam)
+def gradient_penalty(grad, lam=10.0, kind='two_sided', target=1.0):
+    """kind 'two_sided' (WGAN-GP; at the DRAGAN point, DRAGAN), 'one_sided' (WGAN-LP) or 'squared' (R1 / R2: lam is gamma / 2).
+    The two-sided penalty at target 1 is GPLoss, the reference's own term, on its own kernel."""
+    if kind == 'two_sided' and target == 1.0:
+        return GPLoss.apply(grad, lam)
+    return GradPenalty.apply(grad, lam, target, kind)

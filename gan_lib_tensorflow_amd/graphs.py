@@ -40,18 +40,20 @@ def capture(pool=None):
     torch.cuda.graph_pool_handle() shared by graphs that read each other's tensors.
     The Python garbage collector is paused: a cyclic-GC pass in the middle of a capture can destroy an older trainer's
     CUDAGraph / return its pool memory while the stream is capturing, which aborts the process (torch only collects once, on
-    entry).  No eager collective is left on the RCCL watchdog's list when the capture starts, and thread_local because that
-    watchdog's thread polls events concurrently under data parallel."""
+    entry).  The pause spans the whole `with torch.cuda.graph`, its exit included: the stream is still capturing inside
+    capture_end, and a collector switched back on before it ran its pass right there.  No eager collective is left on the RCCL
+    watchdog's list when the capture starts, and thread_local because that watchdog's thread polls events concurrently under data
+    parallel."""
     g = torch.cuda.CUDAGraph()
     was = gc.isenabled()
     parallel.drain_collective_watchdog()
-    with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
-        gc.disable()
-        try:
+    gc.disable()                         # (torch's own gc.collect() on entry is an explicit call: it still runs)
+    try:
+        with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
             yield g
-        finally:
-            if was:
-                gc.enable()
+    finally:
+        if was:
+            gc.enable()
 
 
 def capture_failed(what, e, allow_eager_fallback):

@@ -1746,6 +1746,36 @@ def gp_loss(grad, lam=10.0):
     return loss, dg
 
 
+GRAD_PENALTY_KINDS = {'two_sided': 0, 'one_sided': 1, 'squared': 2}      # the `kind` of gank_grad_penalty by name
+
+
+def grad_penalty(grad, lam, target=1.0, kind='two_sided'):
+    """grad bf16 [N, ...] -> (loss fp32[1], d loss / d grad fp32): lam * mean_n of (s_n - target)^2 ('two_sided'),
+    max(0, s_n - target)^2 ('one_sided') or sum_d g^2 ('squared': no square root, `target` unused), s_n = sqrt(sum_d g^2 + 1e-10)"""
+    if kind not in GRAD_PENALTY_KINDS:
+        raise ValueError(f"grad_penalty: kind {kind!r}: one of {', '.join(GRAD_PENALTY_KINDS)}")
+    n = grad.shape[0]
+    d = grad.numel() // n
+    loss = torch.empty(1, dtype=F32, device=grad.device)
+    dg = torch.empty(grad.shape, dtype=F32, device=grad.device)
+    ws = torch.empty(n, dtype=F32, device=grad.device)
+    _lib.check(lib().gank_grad_penalty(_p(grad, BF16, "grad"), _p(loss), _p(dg), _p(ws), n, d, float(lam), float(target), GRAD_PENALTY_KINDS[kind],
+                                       _stream()), "grad_penalty")
+    return loss, dg
+
+
+def dragan_perturb(real, u):
+    """real bf16, u fp32 in [0, 1) of as many elements -> real + 0.5 * std(real) * u (bf16; the population standard deviation of all
+    elements, computed on the device)"""
+    total = real.numel()
+    if u.numel() != total:
+        raise ValueError(f"dragan_perturb: u has {u.numel()} elements, real {total}")
+    out = torch.empty_like(real)
+    ws = torch.empty(2 * ((total + 4095) // 4096) + 1, dtype=F32, device=real.device)
+    _lib.check(lib().gank_dragan_perturb(_p(real, BF16, "real"), _p(u, F32, "u"), _p(out), _p(ws), total, _stream()), "dragan_perturb")
+    return out
+
+
 def lerp_rows(real, fake, alpha):
     n = real.shape[0]
     out = torch.empty_like(real)

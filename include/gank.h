@@ -755,6 +755,14 @@ int gank_loss_grad_scale(const float* dlogits_f32, const float* g, void* dlogits
  *   10-22) for `groups` towers in one launch; stats [groups][2][C], count = rows per tower (for the unbiased variance).
  *   gank_gp_loss: loss <- lambda * mean_n (sqrt(sum_d g[n,d]^2 + 1e-10) - 1)^2, dgrad <- its derivative (fp32 [N,D]: scaled by
  *   the upstream gradient and rounded once by gank_loss_grad_scale); ws fp32 [N].
+ *   gank_grad_penalty: the other gradient penalties, on the layout of gank_gp_loss (grad bf16 [N,D], loss fp32 [1], dgrad fp32 [N,D] =
+ *   d loss / d grad, ws fp32 [N]).  With s_n = sqrt(sum_d g[n,d]^2 + 1e-10):  kind 0 two-sided lambda * mean_n (s_n - target)^2 (target 1:
+ *   the arithmetic of gank_gp_loss; DRAGAN);  kind 1 one-sided lambda * mean_n max(0, s_n - target)^2 (WGAN-LP: a row with s_n <= target
+ *   contributes exactly 0 and has dgrad exactly 0);  kind 2 squared norm lambda * mean_n sum_d g[n,d]^2 (R1 / R2: no square root, no
+ *   epsilon, `target` unused, dgrad = 2 lambda / N * g, an all-zero row gives exactly 0 for both).  fp32 accumulation in a fixed order.
+ *   gank_dragan_perturb: out (bf16) = real + 0.5 * sigma * u over `total` elements, sigma = the population standard deviation (ddof 0)
+ *   of all of them, computed on the device (fp32 partials of 4096 elements, summed and turned into the variance in double, fixed
+ *   order) and never read by the host; u fp32 in [0, 1); real, u, out 16-byte aligned; ws fp32 [2 * ceil(total / 4096) + 1].
  *   gank_lerp_rows: out[n,:] = real[n,:] + alpha[n] * (fake[n,:] - real[n,:]).
  *   gank_sum_hw / gank_bcast_hw: y[n,c] = scale * sum_hw x[n,hw,c] (tf.reduce_mean(axis=[1,2]), model.py:72) and its adjoint.
  *   gank_rng_uniform_f32: U[0,1) from the device RNG state (advances it). */
@@ -763,6 +771,9 @@ int gank_bn_bwd_bwd(const void* ggI, const void* dy, const void* x, const float*
 int gank_bn_moving_update(const float* stats, float* moving_mean, float* moving_var, float* biased, float* local_step, int C,
                           int groups, long count, float decay, float eps, void* stream);
 int gank_gp_loss(const void* grad, float* loss, void* dgrad, float* ws, int N, long D, float lambda, void* stream);
+int gank_grad_penalty(const void* grad, float* loss, void* dgrad, float* ws, int N, long D, float lambda, float target, int kind,
+                      void* stream);
+int gank_dragan_perturb(const void* real, const float* u, void* out, float* ws, long total, void* stream);
 int gank_lerp_rows(const void* real, const void* fake, const float* alpha, void* out, int N, long D, void* stream);
 int gank_sum_hw(const void* x, void* y, int N, int HW, int C, float scale, void* stream);
 int gank_bcast_hw(const void* g, void* y, int N, int HW, int C, float scale, void* stream);
