@@ -5,7 +5,8 @@ One step (train.py:194-204) = 1 generator update (skipped at step 0) + n_dis = 5
                    + 10 * mean((||grad_x D(x_hat)||_2 - 1)^2),  x_hat = real + alpha (fake - real)   (:99-107)
                    + mean softmax cross-entropy of the class head on the real batch          (:111-114)
     generator loss = -mean(D(G(z))) + acgan_scale_G * cross-entropy of the class head on the fakes (:117-121)
-(the second term is the default of `ACGANTrainer(penalty=...)`: PENALTIES below has the one-sided, DRAGAN, R1 and R2 terms and 'none')
+(the second term is the default of `ACGANTrainer(penalty=...)`: PENALTIES below has the one-sided, DRAGAN, R1 and R2 terms and 'none';
+`ACGANTrainer(consistency='cr' | 'bcr')` adds consistency regularisation, CONSISTENCY below, to the critic loss)
 both with tf.train.AdamOptimizer(beta1=0, beta2=0.9) at a learning rate that decays linearly from 4e-4 to 2e-4 over
 max_iter / 2 generator steps (tf.train.polynomial_decay on `global_step`, :141-148).
 
@@ -71,16 +72,58 @@ def check_penalty(penalty, penalty_weight, penalty_every):
         raise ValueError(f"penalty_weight {penalty_weight!r} with penalty {penalty!r}: a positive weight (penalty='none' switches the term off)")
 
 
+# Consistency regularisation of the critic, a further summand of its loss on every update:
+#   'cr'   w_real * mean_i (D(x_i) - D(T(x_i)))^2                       Zhang et al. 2020 (CR-GAN), eq. 7
+#   'bcr'  the same + w_fake * mean_i (D(G(z_i)) - D(T(G(z_i))))^2       Zhao et al. 2020 (bCR), eq. 1-2
+# D the adversarial logit, T a random horizontal flip and a random shift by up to consistency_shift whole pixels in each axis with
+# the outside mirrored (kernels.cr_draw / cr_augment).  The augmented images are leaves; gradients flow into both passes.
+CONSISTENCY = ('none', 'cr', 'bcr')
+IMAGE_SIZE = 32
+
+
+def check_consistency(consistency, consistency_weight, consistency_shift):
+    """the constructor's checks, before any device work -> (w_real, w_fake)"""
+    if consistency not in CONSISTENCY:
+        raise ValueError(f"consistency {consistency!r}: one of {', '.join(CONSISTENCY)}")
+    if consistency == 'none':
+        return 0.0, 0.0                  # (asks for no weight and no shift)
+    pair = tuple(consistency_weight) if isinstance(consistency_weight, (tuple, list)) else (consistency_weight, consistency_weight)
+    if len(pair) != 2 or any(isinstance(w, bool) or not isinstance(w, numbers.Real) or not 0 < w < float('inf') for w in pair):
+        raise ValueError(f"consistency_weight {consistency_weight!r} with consistency {consistency!r}: a positive weight, or a pair "
+                         "(w_real, w_fake) of them (consistency='none' switches the term off)")
+    s = consistency_shift
+    if isinstance(s, bool) or not isinstance(s, numbers.Real) or int(s) != s or not 0 <= s < IMAGE_SIZE:
+        raise ValueError(f"consistency_shift {s!r}: a whole number of pixels, 0 .. {IMAGE_SIZE - 1} (the mirror rule ends at the image's size)")
+    return float(pair[0]), float(pair[1])
+
+
+class _Losses(dict):
+    """the reported loss terms.  With consistency='none' the dict holds the terms it always held, and a lookup of a consistency term
+    answers a zero constant without storing it."""
+    ABSENT = ('consistency', 'consistency_real', 'consistency_fake')
+
+    def __missing__(self, key):
+        if key in self.ABSENT and 'd_loss_gan' in self:
+            return Fn.constant_like(self['d_loss_gan'], 0.0)
+        raise KeyError(key)
+
+
 class ACGANTrainer(trainer.SampleMetrics, trainer.GraphTrainer):
     def __init__(self, batch_size=64, z_dim=128, acgan_scale_G=0.1, n_dis=5, max_iter=100000, device="cuda", seed=0,
                  process_group=None, state=None, use_graphs=True, allow_eager_fallback=False, penalty='wgan-gp', penalty_weight=10.0,
-                 penalty_every=1):
+                 penalty_every=1, consistency='none', consistency_weight=10.0, consistency_shift=4):
         """penalty: the critic's gradient regulariser (PENALTIES), `penalty_weight` its weight.  penalty_every = k > 1 is the lazy
         regularisation of StyleGAN2 (Karras et al. 2020, appendix B): the term is added on the critic updates whose count is a
         multiple of k, with weight k * penalty_weight; the others run the 'none' form.  `state` may be a `state_dict()` of this
-        trainer: the variables and the count of critic updates."""
+        trainer: the variables and the count of critic updates.
+        consistency: 'cr' or 'bcr' adds consistency regularisation (CONSISTENCY) to every critic update, lazy or not, at
+        `consistency_weight` (one weight, or (w_real, w_fake)) under flips and shifts of up to `consistency_shift` pixels."""
         check_penalty(penalty, penalty_weight, penalty_every)
+        self.consistency_weights = check_consistency(consistency, consistency_weight, consistency_shift)
         super().__init__(device, seed, process_group, use_graphs, allow_eager_fallback)
+        self.losses = _Losses()
+        self.consistency_tables, self._d_tables = {}, {}       # the augmentations of the last critic update: 'real' (and 'fake') -> int32 [B, 3]
+        self.consistency, self.consistency_shift = consistency, int(consistency_shift) if consistency != 'none' else 0
         self.batch, self.z_dim, self.scale_g, self.n_dis, self.max_iter = batch_size, z_dim, acgan_scale_G, n_dis, max_iter
         self.penalty, self.penalty_every = penalty, int(penalty_every)
         self.penalty_weight = float(penalty_weight) if isinstance(penalty_weight, numbers.Real) else 0.0      # ('none' asks for no weight)
@@ -128,8 +171,9 @@ class ACGANTrainer(trainer.SampleMetrics, trainer.GraphTrainer):
         return polynomial_decay(self.global_step, decay_steps=self.max_iter // 2)
 
     # ---- the two losses (eager; explicit inputs override the device RNG for parity tests) -----------------------------
-    def d_loss(self, real, real_labels, z=None, fake_labels=None, alpha=None, u=None, penalise=True):
-        """penalise=False: the form of an update that carries no penalty (`penalty='none'`, and the updates lazy regularisation skips)"""
+    def d_loss(self, real, real_labels, z=None, fake_labels=None, alpha=None, u=None, penalise=True, table_real=None, table_fake=None):
+        """penalise=False: the form of an update that carries no penalty (`penalty='none'`, and the updates lazy regularisation skips).
+        table_real, table_fake: the augmentations of the consistency term, int32 [B, 3] (drawn behind the other draws when not given)"""
         set_default_store(self.store)
         b = real.shape[0]
         m = self.model
@@ -142,15 +186,20 @@ class ACGANTrainer(trainer.SampleMetrics, trainer.GraphTrainer):
             alpha = K.rng_uniform(b, self.rng_state)
         if u is None and point == 'perturbed':
             u = K.rng_uniform(real.numel(), self.rng_state)
+        if table_real is None and self.consistency != 'none':
+            table_real = K.cr_draw(b, self.consistency_shift, self.rng_state)
+        if table_fake is None and self.consistency == 'bcr':
+            table_fake = K.cr_draw(b, self.consistency_shift, self.rng_state)
         with torch.no_grad():            # d_train_op differentiates w.r.t. d_vars only (train.py:148)
             x_fake = m.get_generator(z, fake_labels)
         disc_real, ac_real = m.get_discriminator(real, real_labels, update_collection=None)
         disc_fake, _ = m.get_discriminator(x_fake, fake_labels, update_collection='NO_OPS', reuse=True)
         d_gan = Fn.hinge_d_loss(Fn.concat_rows(disc_real, disc_fake), b)
+        cons = self._consistency_terms(real, real_labels, disc_real, table_real, x_fake, fake_labels, disc_fake, table_fake)
         if kind is None:
             d_ac = Fn.softmax_xent(ac_real, real_labels)
             self.losses.update(d_loss_gan=d_gan.detach(), d_loss_acgan=d_ac.detach(), gradient_penalty=Fn.constant_like(d_gan.detach(), 0.0))
-            return Fn.weighted_sum([d_gan, d_ac])
+            return Fn.weighted_sum([d_gan, d_ac] + cons)
         # the penalised point: a third pass over the critic, differentiated twice
         if point == 'interpolates':
             x_pen, pen_labels = K.lerp_rows(real, x_fake, alpha), real_labels
@@ -171,7 +220,27 @@ class ACGANTrainer(trainer.SampleMetrics, trainer.GraphTrainer):
             gp = F2.gradient_penalty(grads, self.penalty_weight * self.penalty_every, kind, 1.0)
         d_ac = Fn.softmax_xent(ac_real, real_labels)
         self.losses.update(d_loss_gan=K.weighted_sum_f32([d_gan.detach(), gp.detach()], [1.0, 1.0]), d_loss_acgan=d_ac.detach(), gradient_penalty=gp.detach())
-        return Fn.weighted_sum([d_gan, gp, d_ac])
+        return Fn.weighted_sum([d_gan, gp, d_ac] + cons)
+
+    def _consistency_terms(self, real, real_labels, disc_real, table_real, x_fake, fake_labels, disc_fake, table_fake):
+        """-> [] ('none': nothing is launched or reported) or [the term]: one more critic pass over the augmented real batch, for 'bcr'
+        another over the augmented fakes; each a call of its own, so the critic's batch norm sees that batch by itself, and 'NO_OPS'
+        with reuse, so the spectral norm's u is not advanced again"""
+        if self.consistency == 'none':
+            return []
+        w_real, w_fake = self.consistency_weights
+        m = self.model
+        aug_real, _ = m.get_discriminator(K.cr_augment(real, table_real, self.consistency_shift), real_labels, 'NO_OPS', reuse=True)
+        c_real = F2.consistency_loss(disc_real, aug_real, w_real)
+        self.consistency_tables = dict(real=table_real) if self.consistency == 'cr' else dict(real=table_real, fake=table_fake)
+        if self.consistency == 'cr':
+            self.losses.update(consistency=c_real.detach(), consistency_real=c_real.detach(), consistency_fake=Fn.constant_like(c_real.detach(), 0.0))
+            return [c_real]
+        aug_fake, _ = m.get_discriminator(K.cr_augment(x_fake, table_fake, self.consistency_shift), fake_labels, 'NO_OPS', reuse=True)
+        c_fake = F2.consistency_loss(disc_fake, aug_fake, w_fake)
+        cons = Fn.weighted_sum([c_real, c_fake])
+        self.losses.update(consistency=cons.detach(), consistency_real=c_real.detach(), consistency_fake=c_fake.detach())
+        return [cons]
 
     def g_loss(self, z=None, fake_labels=None):
         set_default_store(self.store)
@@ -201,7 +270,13 @@ class ACGANTrainer(trainer.SampleMetrics, trainer.GraphTrainer):
             loss.backward(gradient=Fn.unit_seed(loss))
             self.losses['d_loss'] = loss.detach()
         # (runs on the eager and on the capturing call of a form, not on a replay: d_step puts these back after every update)
-        self._d_losses['d' if penalise else 'd_plain'] = {k: self.losses[k] for k in ('d_loss', 'd_loss_gan', 'd_loss_acgan', 'gradient_penalty')}
+        self._d_losses[self._d_key(penalise)] = {k: self.losses[k] for k in ('d_loss', 'd_loss_gan', 'd_loss_acgan', 'gradient_penalty') + (
+            _Losses.ABSENT if self.consistency != 'none' else ())}
+        self._d_tables[self._d_key(penalise)] = self.consistency_tables
+
+    def _d_key(self, penalise):
+        """the captured form of a critic update: 'd' / 'd_plain' as ever, with the consistency term in it 'd_cr' / 'd_plain_cr' (or _bcr)"""
+        return ('d' if penalise else 'd_plain') + ('' if self.consistency == 'none' else '_' + self.consistency)
 
     def _d_fwd_bwd_plain(self):
         self._d_fwd_bwd(penalise=False)
@@ -218,14 +293,16 @@ class ACGANTrainer(trainer.SampleMetrics, trainer.GraphTrainer):
     def d_step(self, real_u8, labels):
         """one critic update on a uint8 [B, 3072] CHW-planar batch + int labels (train.py:199-204).  Two forms, each a captured graph
         of its own: 'd' carries the penalty, 'd_plain' does not (penalty='none'; under lazy regularisation every update whose count
-        is no multiple of penalty_every).  The count lives on the host and picks the form outside any capture."""
+        is no multiple of penalty_every).  The count lives on the host and picks the form outside any capture.  The consistency term is
+        part of both forms (their keys then end in '_cr' / '_bcr')."""
         self.real_u8.copy_(real_u8, non_blocking=True)
         self.real_labels.copy_(labels, non_blocking=True)
         penalise = self.penalty != 'none' and self.d_updates % self.penalty_every == 0
-        key = 'd' if penalise else 'd_plain'
+        key = self._d_key(penalise)
         self._update(key, self._d_fwd_bwd if penalise else self._d_fwd_bwd_plain, self.d_opt)
         self.d_updates += 1
         self.losses.update(self._d_losses[key])          # a replay wrote the tensors of ITS form, whichever form ran last in Python
+        self.consistency_tables = self._d_tables[key]
         return self.losses['d_loss']
 
     def state_dict(self):

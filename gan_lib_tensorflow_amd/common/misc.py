@@ -41,3 +41,22 @@ def gradient_penalty(gradients, weight=10.0, kind='two_sided', target=1.0):
       'squared'    weight * mean(sum(g^2))                R1 at the real batch, R2 at the generated one; weight = gamma / 2"""
     from .. import functional2 as F2
     return F2.gradient_penalty(gradients, weight, kind, target)
+
+
+def consistency_loss(logits, logits_aug, weight=10.0):
+    """weight * mean_i ||D(x_i) - D(T(x_i))||^2  -- consistency regularisation (Zhang et al. 2020, CR-GAN, eq. 7): `logits` the critic's
+    output on a batch, `logits_aug` its output on `augment` of the same batch, [B] or [B, C], 16-bit or float32.  On the real batch
+    alone it is CR; with a second term on the generated batch (its own weight) bCR (Zhao et al. 2020).  Gradients flow into both
+    passes; the term is differentiated once (it is no operand of a gradient penalty)."""
+    from .. import functional2 as F2
+    return F2.consistency_loss(logits, logits_aug, weight)
+
+
+def augment(images, table, max_shift=None):
+    """T of consistency_loss: NHWC 16-bit images and an int32 table [B, 3] = (flip, dx, dy), one row an image (kernels.cr_draw(B, shift,
+    rng_state) draws one) -> out[b, y, x] = images[b, R(y - dy), R(xf - dx)], xf = W - 1 - x where flip != 0: each image shifted by
+    (dx, dy) whole pixels, the pixels that come from outside mirrored as np.pad(mode='reflect') mirrors them (R), then flipped left to
+    right where flip != 0.  A gather: exact, and no gradient flows through it (the
+    augmented images are leaves of the critic update).  max_shift: the largest shift in the table, below min(H, W)."""
+    from .. import kernels as K
+    return K.cr_augment(images, table, max_shift)

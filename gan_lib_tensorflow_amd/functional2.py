@@ -491,6 +491,32 @@ class GradPenalty(Function):
         return K.loss_grad_scale(dg32, _c(g.to(torch.float32)).reshape(1)), None, None, None
 
 
+class ConsistencyLoss(Function):
+    """weight * mean_n sum_c (a - b)^2 of two sets of logits (kernels.consistency_loss; CR-GAN, Zhang et al. 2020, eq. 7).  16-bit
+    logits (the critic's) are widened to fp32 first, which is exact.  First order only: the backward is the saved fp32 derivatives
+    times the upstream scalar, in the dtype of the inputs (GPLoss is the model), and is not differentiable again."""
+
+    @staticmethod
+    def forward(ctx, a, b, weight):
+        if a.dtype != b.dtype or a.dtype not in (K.BF16, torch.float32):
+            raise ValueError(f"consistency_loss: logits of {a.dtype} and {b.dtype}: both {K.BF16} or both float32")
+        ctx.widened = a.dtype != torch.float32
+        a, b = _c(a), _c(b)
+        if ctx.widened:
+            a, b = K.to_f32(a), K.to_f32(b)
+        loss, da, db = K.consistency_loss(a, b, weight)
+        ctx.save_for_backward(da, db)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        da, db = ctx.saved_tensors
+        g = _c(g.to(torch.float32)).reshape(1)
+        scale = K.loss_grad_scale if ctx.widened else K.scale_f32           # fp32 product; one rounding to 16 bits where the logits had 16
+        return (scale(da, g) if ctx.needs_input_grad[0] else None), (scale(db, g) if ctx.needs_input_grad[1] else None), None
+
+
 # ---- functional forms -------------------------------------------------------------------------------------------
 class AddF(Function):
     """a + b (one launch); linear, so its backward is differentiable as it stands"""
@@ -564,3 +590,8 @@ def gradient_penalty(grad, lam=10.0, kind='two_sided', target=1.0):
     if kind == 'two_sided' and target == 1.0:
         return GPLoss.apply(grad, lam)
     return GradPenalty.apply(grad, lam, target, kind)
+
+
+def consistency_loss(a, b, weight=10.0):
+    """weight * mean_n sum_c (a - b)^2 -> fp32[1]; gradients reach both a and b (first order)"""
+    return ConsistencyLoss.apply(a, b, weight)

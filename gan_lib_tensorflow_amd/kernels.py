@@ -4,6 +4,8 @@ current torch stream.  Nothing here has a CPU path.  The argument types, the des
 flag constants used below are the ones _lib derives from the header; a wrapper for a new entry point
 needs its declaration there and nothing else."""
 import ctypes as C
+import math
+import numbers
 
 import torch
 
@@ -1774,6 +1776,59 @@ def dragan_perturb(real, u):
     ws = torch.empty(2 * ((total + 4095) // 4096) + 1, dtype=F32, device=real.device)
     _lib.check(lib().gank_dragan_perturb(_p(real, BF16, "real"), _p(u, F32, "u"), _p(out), _p(ws), total, _stream()), "dragan_perturb")
     return out
+
+
+def _whole(v):
+    return not isinstance(v, bool) and isinstance(v, numbers.Real) and int(v) == v
+
+
+def cr_draw(n, shift, rng_state):
+    """the augmentations of a batch of n (consistency regularisation): int32 [n, 3] = (flip in {0, 1}, dx, dy in [-shift, shift]) from
+    the device RNG state, which advances by 1.  Row i takes Philox call i of the draw: flip = word 0 >> 31, dx = mulhi(word 1,
+    2 shift + 1) - shift, dy = the same of word 2 (tests/consistency_ref.py restates it on the host)"""
+    if not _whole(n) or n < 1:
+        raise ValueError(f"cr_draw: n {n!r}: a whole number of rows, at least 1")
+    if not _whole(shift) or not 0 <= shift <= 32767:
+        raise ValueError(f"cr_draw: shift {shift!r}: a whole number of pixels, 0 .. 32767")
+    table = torch.empty((int(n), 3), dtype=I32, device=rng_state.device)
+    _lib.check(lib().gank_cr_draw(_p(table), int(n), int(shift), _p(rng_state, torch.int64, "rng_state"), _stream()), "cr_draw")
+    return table
+
+
+def cr_augment(x, table, max_shift=None):
+    """x 16-bit NHWC [B, H, W, C], table int32 [B, 3] = (flip, dx, dy) -> out[b, y, x] = x[b, R(y - dy, H), R(xf - dx, W)], xf = W - 1 - x
+    where flip, R the reflection of np.pad(mode='reflect').  Exact (a gather).  max_shift: the largest |dx|, |dy| the table holds (the
+    `shift` it was drawn with); it must be below min(H, W), where the reflection ends, and entries beyond it are clamped to it.
+    None: min(H, W) - 1, every shift the reflection is defined for."""
+    if x.dim() != 4:
+        raise ValueError(f"cr_augment: x has shape {tuple(x.shape)}: NHWC [B, H, W, C]")
+    b, h, w, c = x.shape
+    if tuple(table.shape) != (b, 3):
+        raise ValueError(f"cr_augment: table has shape {tuple(table.shape)}, x {b} images: [{b}, 3] = (flip, dx, dy)")
+    if table.dtype != I32:
+        raise ValueError(f"cr_augment: table is {table.dtype}: int32")
+    if max_shift is None:
+        max_shift = min(h, w) - 1
+    if not _whole(max_shift) or not 0 <= max_shift < min(h, w):
+        raise ValueError(f"cr_augment: shift {max_shift!r} on {h} x {w} images: a whole number below min(H, W), where the reflection ends")
+    out = torch.empty_like(x)
+    _lib.check(lib().gank_cr_augment(_p(x, BF16, "x"), _p(table, I32, "table"), _p(out), b, h, w, c, int(max_shift), _stream()), "cr_augment")
+    return out
+
+
+def consistency_loss(a, b, weight):
+    """a, b fp32 [B] or [B, C] -> (loss fp32[1] = weight / B * sum (a - b)^2, d loss / d a = 2 weight / B * (a - b), d loss / d b = its
+    negative), one launch, bit-reproducible"""
+    if a.shape != b.shape or a.dim() not in (1, 2) or a.numel() == 0:
+        raise ValueError(f"consistency_loss: a {tuple(a.shape)}, b {tuple(b.shape)}: two [B] or [B, C] tensors of one shape")
+    if isinstance(weight, bool) or not isinstance(weight, numbers.Real) or not math.isfinite(weight):
+        raise ValueError(f"consistency_loss: weight {weight!r}: a finite number")
+    n = a.shape[0]
+    loss = torch.empty(1, dtype=F32, device=a.device)
+    da, db = torch.empty_like(a), torch.empty_like(a)
+    _lib.check(lib().gank_consistency_loss(_p(a, F32, "a"), _p(b, F32, "b"), _p(loss), _p(da), _p(db), n, a.numel() // n, float(weight), _stream()),
+               "consistency_loss")
+    return loss, da, db
 
 
 def lerp_rows(real, fake, alpha):

@@ -779,6 +779,26 @@ int gank_sum_hw(const void* x, void* y, int N, int HW, int C, float scale, void*
 int gank_bcast_hw(const void* g, void* y, int N, int HW, int C, float scale, void* stream);
 int gank_rng_uniform_f32(float* y, long n, uint64_t* rng_state, void* stream);
 
+/* ---- consistency regularisation of the critic (csrc/consistency.hip) ------------------------------------------------------
+ * L_cr = w * mean_i ||D(x_i) - D(T(x_i))||^2 on the real batch (Zhang et al. 2020, "Consistency Regularization for GANs", section 3.1,
+ * eq. 5-7), and the same term on the generated batch beside it for bCR (Zhao et al. 2020, "Improved Consistency Regularization for
+ * GANs", section 3.1, eq. 1-2).  T: a random horizontal flip and a random shift by whole pixels with the outside mirrored (the
+ * augmentation of CR-GAN's CIFAR-10 runs, section 4.1 there).
+ *   gank_cr_draw (the parameters of T, CR-GAN section 4.1): table int32 [n,3] = (flip in {0,1}, dx, dy in [-shift, shift]) from the device
+ *   RNG state, which it advances by 1 on the device (one block; a captured graph draws afresh on every replay).  Row i takes Philox
+ *   call i of the draw (one call of four words a row): flip = word 0 >> 31, dx = mulhi(word 1, 2 shift + 1) - shift, dy = the same of
+ *   word 2, word 3 unused; the probabilities of two shifts differ by at most 2^-32.  0 <= shift <= 32767.
+ *   gank_cr_augment (T itself, CR-GAN section 3.1 eq. 5): out[b,y,x,:] = x[b, R(y - dy, H), R(xf - dx, W), :] over 16-bit NHWC [B,H,W,C],
+ *   xf = W - 1 - x where flip != 0, R(i, n) = -i below 0 and 2 (n - 1) - i from n on (np.pad(mode='reflect'): the edge is not repeated).
+ *   A gather of raw 16-bit elements: exact.  max_shift < min(H, W) is the largest |dx|, |dy| the caller's table holds; an entry beyond
+ *   it is clamped to it, so no table reads outside the image.  out != x; H + W C <= 16384 (the row and column tables in LDS).
+ *   gank_consistency_loss (the term, CR-GAN eq. 7 / bCR eq. 1-2): a, b fp32 [B,C] (C = 1: the critic's logit) -> loss fp32 [1] = w / B *
+ *   sum_i sum_c (a - b)^2, da fp32 [B,C] = 2 w / B * (a - b), db = -da (the sign bit turned).  One launch of one block, fp32 sums in a
+ *   fixed order, no atomics: bit-reproducible; ceil(B C / 256) + 13 roundings to the loss, 3 to a derivative, exact zeros where a == b. */
+int gank_cr_draw(int32_t* table, long n, int shift, uint64_t* rng_state, void* stream);
+int gank_cr_augment(const void* x, const int32_t* table, void* out, int B, int H, int W, int C, int max_shift, void* stream);
+int gank_consistency_loss(const float* a, const float* b, float* loss, float* da, float* db, int B, int C, float w, void* stream);
+
 /* ---- small operators of the PGGAN (config 4) and Pix2Pix (config 5) paths --------------------------------------------
  * axpby: y = alpha*a + beta*b (b may be NULL): the fade-in blend (1-alpha)*toRGB2 + alpha*toRGB1 (PGGAN/model_nvidia.py:116,206).
  * minibatch_std (model_nvidia.py:20-29): y [B,HW,C+1] = concat(x, mean_{hwc} sqrt(var_batch(x)+1e-8)); ws fp32 [HW*C + 2] is
